@@ -8,10 +8,15 @@ episode), fused into one kernel launch per point; the batch summary is integer-e
 all-reduced once over RCCL. Weak scaling: E is per GPU.
 
 gamma = 1 is rejected by the reference (gym/ocaml/cpr_gym/envs.py:73-75,
-network.ml:69-72), so the timed sweep runs gamma in {0, 0.5}; the gamma = 1 column runs
-after it, untimed for `value`, in the flagged abstract-gamma mode (CPR_NET_ABSTRACT_GAMMA,
-include/cpr_hip.h) and is reported separately ("abstract_gamma_1") beside the Eyal-Sirer
-closed form.
+network.ml:69-72), so the timed sweep runs gamma in {0, 0.5}; under --full the gamma = 1
+column runs after it, untimed for `value`, in the flagged abstract-gamma mode
+(CPR_NET_ABSTRACT_GAMMA, include/cpr_hip.h) and is reported separately
+("abstract_gamma_1") beside the Eyal-Sirer closed form.
+
+A plain run sets up, warms up, times the steps and prints the line. --full adds what takes
+runs of its own after the timed region: the abstract-gamma column, the CPU baseline and
+the other BASELINE configs ("other_configs"). --dump-outputs DIR writes the per-point
+summaries the last timed step returned as DIR/<name>.npy.
 
 Prints one JSON line (rank 0).
 """
@@ -336,6 +341,29 @@ def pmc_traffic(episodes):
     return None, None, None
 
 
+def dump_outputs(path, points, summaries):
+    """--dump-outputs: the last timed step's outputs, i.e. one summary per sweep point
+    (all ranks' episodes of that step), as float64 .npy files of [point][word] in the order
+    of Summary.to_array() (fields, then the histogram). The words are 64-bit integers, so
+    beside their float64 value (rounded above 2^53) the two 32-bit halves are written,
+    which float64 holds exactly: two builds agree iff summary_hi32 and summary_lo32 do."""
+    from cpr_amd import parallel
+
+    os.makedirs(path, exist_ok=True)
+    words = np.stack([s.to_array() for s in summaries]).view(np.uint64)
+    stats = [parallel.summary_stats(s) for s in summaries]
+    arrays = {
+        "points": np.array(points, dtype=np.float64),  # [point] (alpha, gamma)
+        "summary": words.view(np.int64).astype(np.float64),
+        "summary_hi32": (words >> np.uint64(32)).astype(np.float64),
+        "summary_lo32": (words & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "mean_rel_revenue": np.array([[st["mean"], st["stderr"]] for st in stats],
+                                     dtype=np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _spawn_ranks(n, argv):
     """`--gpus N` without a launcher (no WORLD_SIZE in the environment): start N fresh rank
     processes of this script, one per GPU, with the torchrun variables set, as the
@@ -407,10 +435,17 @@ def main():
     # 256 CUs: 262,144 or 327,680 lanes), and the driver's 20 steps make BASELINE configs[1]'s
     # 10^8 episodes per (alpha, gamma) point on every GPU
     ap.add_argument("--episodes", type=int, default=5242880, help="per GPU per sweep point")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline does not need: "
+                         "the abstract-gamma gamma = 1 column, the CPU baseline (unless "
+                         "--no-cpu) and BASELINE configs[0], [2]-[4] (unless --no-configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-point summaries to DIR/<name>.npy "
+                         "(float64; see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip BASELINE configs[0], [2]-[4] (other_configs)")
+                    help="with --full: skip BASELINE configs[0], [2]-[4] (other_configs)")
     ap.add_argument("--config-cpu-seconds", type=float, default=2.0)
     ap.add_argument("--gammas", default=",".join(str(g) for g in GAMMAS),
                     help="sweep gammas (A/B runs; the headline is the default)")
@@ -422,6 +457,8 @@ def main():
                          "ranks, init the collective, time and all-reduce EMPTY steps without "
                          "touching a GPU; the line says so and has no value")
     args = ap.parse_args()
+    if args.steps < 1 and not args.launch_check:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: start the ranks ourselves, before anything touches a GPU
@@ -488,20 +525,29 @@ def main():
         one_step(10**6 + w, new_sums())
     sync_all()
     rr0 = rerun_all()
-    sums_dev = new_sums()
+    # the last step accumulates into summaries of its own, so that what it alone returned
+    # can be written out (--dump-outputs); the steps before it share one set
+    sums_dev, last_dev = new_sums(), new_sums()
     parallel.barrier(cdev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        one_step(k, sums_dev)
+        one_step(k, sums_dev if k < args.steps - 1 else last_dev)
     sync_all()
     torch.cuda.synchronize()
     parallel.barrier(cdev)
     dt_local = time.perf_counter() - t0
     dt = parallel.allreduce_max(dt_local, cdev)
     rr1 = rerun_all()  # this rank's exact re-runs of the timed region
-    sums = read(sums_dev)
-    totals = parallel.allreduce_summaries(sums, cdev)  # one packed collective
+    last = read(last_dev)
+    # integer words: the sum over steps is exact (the unsigned fields wrap as int64)
+    sums = [L.Summary.from_array(a.to_array() + b.to_array())
+            for a, b in zip(read(sums_dev), last)]
+    # one packed collective: every point's total, then every point's last step
+    both = parallel.allreduce_summaries(sums + last, cdev)
+    totals, last_totals = both[:len(points)], both[len(points):]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, points, last_totals)
     acts = sum(int(s.activations) for s in totals)
     episodes = sum(int(s.episodes) for s in totals)
 
@@ -517,24 +563,26 @@ def main():
     rows = parallel.gather_rows([rank, dt_local, float(kms.sum()), local_acts,
                                  rr1[0] - rr0[0], rr1[2] - rr0[2], float(gpu)], cdev)
 
-    # configs[1]'s gamma = 1 column in the flagged abstract-gamma mode, after the timed
-    # region: same kernel, zero delays, match races decided by gamma coins; its own clock
+    # --full: configs[1]'s gamma = 1 column in the flagged abstract-gamma mode, after the
+    # timed region: same kernel, zero delays, match races decided by gamma coins; its own
+    # clock
     abatches = []
-    for a in ALPHAS:
-        cfg, keep = device.make_config(alpha=a, gamma=1.0, network=L.NET_ABSTRACT_GAMMA,
-                                       defenders=2, max_steps=STEPS_PER_EPISODE, seed=SEED)
-        abatches.append(device.Batch(cfg, ctx=ctx, keep=keep))
-    asums = new_sums()
-    parallel.barrier(cdev)
-    torch.cuda.synchronize()
-    ta = time.perf_counter()
-    for b, sd in zip(abatches, asums):
-        b.run_async(E, rank * E, sd.data_ptr())
-    ctx.synchronize()
-    torch.cuda.synchronize()
-    parallel.barrier(cdev)
-    dta = parallel.allreduce_max(time.perf_counter() - ta, cdev)
-    atotals = parallel.allreduce_summaries(read(asums[:len(abatches)]), cdev)
+    if args.full:
+        for a in ALPHAS:
+            cfg, keep = device.make_config(alpha=a, gamma=1.0, network=L.NET_ABSTRACT_GAMMA,
+                                           defenders=2, max_steps=STEPS_PER_EPISODE, seed=SEED)
+            abatches.append(device.Batch(cfg, ctx=ctx, keep=keep))
+        asums = new_sums()
+        parallel.barrier(cdev)
+        torch.cuda.synchronize()
+        ta = time.perf_counter()
+        for b, sd in zip(abatches, asums):
+            b.run_async(E, rank * E, sd.data_ptr())
+        ctx.synchronize()
+        torch.cuda.synchronize()
+        parallel.barrier(cdev)
+        dta = parallel.allreduce_max(time.perf_counter() - ta, cdev)
+        atotals = parallel.allreduce_summaries(read(asums[:len(abatches)]), cdev)
     traffic, traffic_src, valu_meas = pmc_traffic(E)
     kacts = np.full(len(batches), float(E * (STEPS_PER_EPISODE + 1)))
     act_per_s_kernel = float(kacts.sum() / (kms.sum() / 1e3))
@@ -608,7 +656,10 @@ def main():
                           "exact_reruns": int(r[4]), "exact_rerun_ms": round(r[5], 3)}
                          for r in rows],
             "sweep_mean_rel_revenue": sweep,
-            "abstract_gamma_1": {
+            "full": args.full,
+        }
+        if args.full:
+            out["abstract_gamma_1"] = {
                 "mode": "FLAGGED abstract-gamma (CPR_NET_ABSTRACT_GAMMA): not the reference's "
                         "network, which rejects gamma = 1; zero delays, 2 defenders, a match "
                         "race goes to the attacker's release at every defender (coin < 1)",
@@ -620,14 +671,13 @@ def main():
                                  round(es14(a, 1.0), 6) if a < 0.5 else None]
                     for a, s in zip(ALPHAS, atotals)},
                 "invalid_episodes": sum(int(s.invalid) for s in atotals),
-            },
-        }
-        if not args.no_cpu:
+            }
+        if args.full and not args.no_cpu:
             # host only, after every collective of the timed region: at N > 1 rank 0
             # measures the same bounded oracle sample, so every line of a 1/2/4/8-GPU series
             # carries the CPU baseline of its own job (north_star)
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, points)
-        if not args.no_configs and ws == 1:
+        if args.full and not args.no_configs and ws == 1:
             # the other BASELINE configs on this GPU, after the headline's timed region
             out["other_configs"] = run_other_configs(ctx, args.config_cpu_seconds,
                                                      not args.no_cpu, config_pmc())

@@ -69,6 +69,39 @@ def test_eyal_sirer_closed_form(alpha, gamma, want):
     assert bench.es14(alpha, gamma) == pytest.approx(want, abs=1e-4)
 
 
+def test_dump_outputs_holds_every_summary_word_exactly(tmp_path):
+    # --dump-outputs writes float64 arrays; a 64-bit summary word above 2^53 does not fit
+    # one, so the two 32-bit halves are written too and rebuild every word exactly
+    import numpy as np
+
+    from cpr_amd import _lib as L
+
+    sums = []
+    for i in range(3):
+        s = L.Summary()
+        s.episodes = 4096 + i
+        s.activations = (1 << 53) + 1 + i  # not a float64
+        s.rel_revenue_fx = (1 << 64) - 1 - i  # unsigned, top bit set
+        s.rel_revenue_sq_fx = (1 << 63) + 12345
+        s.reward_defender_fx = -7 - i
+        s.hist[0], s.hist[L.HIST_BINS - 1] = 11, 13 + i
+        sums.append(s)
+    pts = [(0.05, 0.0), (0.5, 0.0), (0.25, 0.5)]
+    bench.dump_outputs(str(tmp_path / "d"), pts, sums)
+    arrs = {p.stem: np.load(p) for p in (tmp_path / "d").glob("*.npy")}
+    assert set(arrs) == {"points", "summary", "summary_hi32", "summary_lo32", "mean_rel_revenue"}
+    assert all(a.dtype == np.float64 for a in arrs.values())
+    assert arrs["points"].tolist() == [list(p) for p in pts]
+    words = (arrs["summary_hi32"].astype(np.uint64) << np.uint64(32)) \
+        | arrs["summary_lo32"].astype(np.uint64)
+    for i, s in enumerate(sums):
+        assert words[i].view(np.int64).tolist() == s.to_array().tolist()
+        back = L.Summary.from_array(words[i].view(np.int64))
+        assert back.rel_revenue_fx == s.rel_revenue_fx and back.activations == s.activations
+        assert arrs["summary"][i, 0] == 4096 + i
+        assert arrs["mean_rel_revenue"][i, 0] == s.rel_revenue_fx / 2**32 / s.episodes
+
+
 def test_driver_record_shape():
     # the last driver record of the previous round has the fields the contract asks for
     recs = sorted(ROOT.glob("BENCH_r*.json"))
@@ -77,8 +110,12 @@ def test_driver_record_shape():
     d = json.loads(recs[-1].read_text())
     line = d.get("parsed") or {}
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
-              "higher_is_better", "scaling", "roofline", "cpu_baseline", "config"):
+              "higher_is_better", "scaling", "roofline", "config"):
         assert k in line, k
+    # the CPU baseline is part of a --full line; a record from before that option (no
+    # "full" key) always carried it
+    if line.get("full", True):
+        assert "cpu_baseline" in line
 
 
 def _bench_cmd(args, env_drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")):
@@ -89,6 +126,15 @@ def _bench_cmd(args, env_drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"
     env["PYTHONPATH"] = str(ROOT) + os.pathsep + env.get("PYTHONPATH", "")
     return subprocess.run([sys.executable, str(ROOT / "bench.py")] + args, cwd=str(ROOT),
                           env=env, capture_output=True, text=True, timeout=300)
+
+
+def test_bench_options():
+    p = _bench_cmd(["--help"])
+    assert p.returncode == 0, p.stderr[-3000:]
+    for opt in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
+        assert opt in p.stdout, opt
+    p = _bench_cmd(["--steps", "0"])  # no timed step: nothing to divide the time by
+    assert p.returncode == 2 and "--steps" in p.stderr
 
 
 def test_bench_starts_its_own_ranks():

@@ -73,11 +73,11 @@ def test_bench_starts_two_ranks_itself():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     # reports the whole job, with rank 0's bounded CPU baseline (measured after the timed
-    # region) in the N-GPU line too
+    # region, under --full) in the N-GPU line too
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
                         "2", "--warmup", "1", "--episodes", "8192", "--cpu-seconds", "2",
-                        "--backend", "gloo"], cwd=ROOT, env=env, capture_output=True, text=True,
-                       timeout=300)
+                        "--backend", "gloo", "--full"], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Round-end style GPU session: smoke, every -m gpu test, the default bench line, then the
+# Round-end style GPU session: smoke, every -m gpu test, the full bench line (bench.py
+# --full: CPU baseline, abstract-gamma column and other_configs; BENCH_ARGS adds to it), then the
 # rocprofv3 passes of tools/profile.sh and (PROFILE_CONFIGS=1) tools/profile_configs.sh.
 # Each GPU step has its own time limit; a fault, abort or timeout (124, 134, 137, 139)
 # stops the script. TAG names the logs (gpurun_out/<TAG>_*); SKIP_TESTS=1 / SKIP_BENCH=1 /
@@ -15,6 +16,7 @@ if [[ -z "${SKIP_TESTS:-}" ]]; then
   rc=$?; echo "pytest rc=$rc" | tee -a gpurun_out/${TAG}_status.log; ok $rc || exit $rc
 fi
 if [[ -z "${SKIP_BENCH:-}" ]]; then
+  BENCH_ARGS="--full ${BENCH_ARGS:-}"
   timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > gpurun_out/${TAG}_bench.log 2>&1
   rc=$?; echo "bench rc=$rc" | tee -a gpurun_out/${TAG}_status.log; [[ $rc -eq 0 ]] || exit $rc
 fi

@@ -3,6 +3,8 @@
 # default bench workload without the CPU leg, one run per variant, via CPR_HIP_LIB.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+# --full: the status line below prints the abstract-gamma column beside the headline
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 for v in ${VARIANTS:-base cheap_rng cheap_log cheap_both base}; do
   for E in ${EPISODES:-393216}; do
   CPR_HIP_LIB=build/var/$v.so timeout -k 10 240 python bench.py --steps 3 --warmup 1 --no-cpu --no-configs ${BENCH_ARGS:-} --episodes $E > gpurun_out/ab_${v}_$E.log 2>&1

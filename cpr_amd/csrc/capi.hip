@@ -177,6 +177,8 @@ struct cpr_batch {
   DevBuf l_alog, l_emem, l_eslots, l_efree;
   int64_t alog_cap = 0;
   int32_t n_exact_slots = 0;
+  // cpr_rollout over the closed-form lanes: per-lane step cursor; summary + lanes-left word
+  DevBuf l_cur, l_rsum;
   bool reset_done = false;
   int32_t tab_n = 4096;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -954,7 +956,8 @@ int cpr_batch_destroy(cpr_batch* b) {
   for (DevBuf* d : {&b->table_dev, &b->tabs_dev, &b->summary,
                     &b->records, &b->lanes, &b->lring, &b->lspill, &b->lreplay,
                     &b->l_obs, &b->l_act, &b->l_rew, &b->l_done, &b->l_mask, &b->l_eps,
-                    &b->l_info, &b->l_alog, &b->l_emem, &b->l_eslots, &b->l_efree, &b->tr_off, &b->tr_miner, &b->tr_delay, &b->tr_pow,
+                    &b->l_info, &b->l_alog, &b->l_emem, &b->l_eslots, &b->l_efree, &b->l_cur,
+                    &b->l_rsum, &b->tr_off, &b->tr_miner, &b->tr_delay, &b->tr_pow,
                     &b->tr_key, &b->tr_ldelay})
     d->release();
   delete b;
@@ -2118,11 +2121,71 @@ const char* cpr_policy_name(int32_t protocol, int32_t index, int32_t* policy_id)
   return kNames[index];
 }
 
+// cpr_rollout over the Nakamoto closed-form lanes: rounds of the closed-form pass and the
+// exact pass (kernels.hip k_nak_rollout, k_nak_rollout_exact) until no lane has steps left.
+// The lanes-left word sits behind the device summary and comes back in the same copy. Every
+// round advances each unfinished lane by at least one step, so n_steps + 1 rounds always
+// suffice: past that bound the call fails instead of spinning. On success the stream is idle
+// and *out holds the call's summary.
+static int nak_rollout_rounds(cpr_batch* b, int64_t n_steps, double* obs, double* reward,
+                              uint8_t* done, cpr_summary* out) {
+  static_assert(sizeof(cpr_summary) % 8 == 0, "the lanes-left word follows the summary");
+  struct {
+    cpr_summary s;
+    unsigned long long left;
+  } host;
+  const int64_t n = b->cfg.n_lanes;
+  hipStream_t st = b->ctx->stream;
+  HIP_TRY(b->l_cur.ensure((size_t)n * sizeof(int64_t)));
+  HIP_TRY(b->l_rsum.ensure(sizeof(host)));
+  HIP_TRY(hipMemsetAsync(b->l_cur.p, 0, (size_t)n * sizeof(int64_t), st));
+  HIP_TRY(hipMemsetAsync(b->l_rsum.p, 0, sizeof(host), st));
+  RollBuffers R;
+  R.cursor = (int64_t*)b->l_cur.p;
+  R.sum = (cpr_summary*)b->l_rsum.p;
+  R.left = (unsigned long long*)((char*)b->l_rsum.p + sizeof(cpr_summary));
+  R.obs = obs;
+  R.reward = reward;
+  R.done = done;
+  R.n_steps = n_steps;
+  const LockBuffers LB = lock_buffers(b);
+  const double* tabs = (const double*)b->tabs_dev.p;
+  for (int64_t round = 0;; ++round) {
+    if (round > n_steps)
+      return fail(CPR_E_STATE, "cpr_rollout: lanes still have steps left after n_steps + 1 "
+                               "rounds of the closed-form and exact passes");
+    if (round > 0) HIP_TRY(hipMemsetAsync(R.left, 0, sizeof(unsigned long long), st));
+    HIP_TRY(launch_nak_rollout(b->P, b->cfg.seed, LB, n, R, b->cfg.unit_observation, tabs,
+                               tabs + b->tab_n, b->tab_n, st));
+    HIP_TRY(launch_nak_rollout_exact(b->P, b->NEP, b->cfg.seed, LB, n, R,
+                                     b->cfg.unit_observation, tabs, tabs + b->tab_n, b->tab_n,
+                                     st));
+    HIP_TRY(hipMemcpyAsync(&host, b->l_rsum.p, sizeof(host), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (host.left == 0) break;
+  }
+  *out = host.s;
+  return CPR_OK;
+}
+
 int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint8_t* done,
                 int outputs_on_device, cpr_summary* summary) {
   if (!b || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
-  if (!b->is_ev && !b->is_eth)
-    return fail(CPR_E_UNSUPPORTED, "cpr_rollout is implemented for Ethereum, B_k and Tailstorm");
+  const bool is_nak = !b->is_ev && !b->is_eth;
+  if (is_nak) {
+    // the closed-form lane's rollout (k_nak_rollout): the gym's networks, policies the lane
+    // can evaluate on its own observation
+    if (b->cfg.protocol != CPR_PROTO_NAKAMOTO)
+      return fail(CPR_E_UNSUPPORTED,
+                  "cpr_rollout is implemented for Nakamoto, Ethereum, B_k and Tailstorm");
+    if (b->nak_ev || (b->cfg.network != CPR_NET_SELFISH_MINING &&
+                      b->cfg.network != CPR_NET_ABSTRACT_GAMMA))
+      return fail(CPR_E_UNSUPPORTED,
+                  "cpr_rollout (Nakamoto): selfish-mining and abstract-gamma networks only");
+    if (b->cfg.policy < CPR_POLICY_HONEST || b->cfg.policy > CPR_POLICY_TABLE)
+      return fail(CPR_E_UNSUPPORTED,
+                  "cpr_rollout (Nakamoto): built-in policies and CPR_POLICY_TABLE only");
+  }
   if (n_steps <= 0) return CPR_OK;
   HIP_TRY(hipSetDevice(b->ctx->device));
   int rc = ensure_lockstep(b);
@@ -2156,7 +2219,11 @@ int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint
   }
   const double* tabs = (const double*)b->tabs_dev.p;
   HIP_TRY(hipEventRecord(b->ev0, st));
-  if (b->is_eth)
+  cpr_summary s;
+  if (is_nak) {
+    rc = nak_rollout_rounds(b, n_steps, obs_dev, reward_dev, done_dev, &s);
+    if (rc) return rc;
+  } else if (b->is_eth)
     HIP_TRY(launch_eth_rollout(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
                                b->bk_slots.p, b->cfg.n_lanes, n_steps, b->cfg.unit_observation,
                                tabs, b->tab_n, obs_dev, reward_dev, done_dev,
@@ -2172,8 +2239,8 @@ int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint
                               tabs, b->tab_n, obs_dev, reward_dev, done_dev,
                               (cpr_summary*)b->summary.p, st));
   HIP_TRY(hipEventRecord(b->ev1, st));
-  cpr_summary s;
-  HIP_TRY(hipMemcpyAsync(&s, b->summary.p, sizeof(s), hipMemcpyDeviceToHost, st));
+  if (!is_nak)
+    HIP_TRY(hipMemcpyAsync(&s, b->summary.p, sizeof(s), hipMemcpyDeviceToHost, st));
   if (!outputs_on_device) {
     if (obs) HIP_TRY(hipMemcpyAsync(obs, obs_dev, (size_t)cells * ol * 8, hipMemcpyDeviceToHost, st));
     if (reward) HIP_TRY(hipMemcpyAsync(reward, reward_dev, (size_t)cells * 8, hipMemcpyDeviceToHost, st));
@@ -2192,7 +2259,7 @@ int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint
   // resident figure is the fused-episode kernel's occupancy of the same lane
   b->last_lanes = b->cfg.n_lanes;
   b->last_resident = (int64_t)b->ctx->cus * 256 *
-                     (b->is_eth ? eth_blocks_per_cu()
+                     (is_nak ? nak_rollout_blocks_per_cu() : b->is_eth ? eth_blocks_per_cu()
                                 : (b->cfg.protocol == CPR_PROTO_TAILSTORM ? ts_blocks_per_cu()
                                                                           : bk_blocks_per_cu()));
   summary->episodes += s.episodes;

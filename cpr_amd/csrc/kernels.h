@@ -117,6 +117,29 @@ hipError_t launch_lock_exact(const eth::EthParams& EP, uint64_t seed, const Lock
                              int64_t n, const int32_t* actions, int unit, const double* tab_nn,
                              const double* tab_sg, int32_t tab_n, const StepBuffers& b,
                              hipStream_t st);
+// what the passes of one cpr_rollout call over the Nakamoto lockstep lanes share (device
+// pointers; obs / reward / done optional, step-major)
+struct RollBuffers {
+  int64_t* cursor;           // [n] steps of this call each lane has taken (zeroed per call)
+  unsigned long long* left;  // lanes the exact pass left on the closed form with steps to take
+  double* obs;               // [n_steps][n][4]
+  double* reward;            // [n_steps][n]
+  uint8_t* done;             // [n_steps][n]
+  cpr_summary* sum;
+  int64_t n_steps;
+};
+// one round of the rollout (kernels.hip k_nak_rollout): the closed-form pass, then the exact
+// pass over the lanes on the exact engine (no launch for a batch without one); the host
+// repeats the round while *R.left != 0 (zeroed before each round)
+hipError_t launch_nak_rollout(const NakParams& P, uint64_t seed, const LockBuffers& B, int64_t n,
+                              const RollBuffers& R, int unit, const double* tab_nn,
+                              const double* tab_sg, int32_t tab_n, hipStream_t st);
+hipError_t launch_nak_rollout_exact(const NakParams& P, const eth::EthParams& EP, uint64_t seed,
+                                    const LockBuffers& B, int64_t n, const RollBuffers& R,
+                                    int unit, const double* tab_nn, const double* tab_sg,
+                                    int32_t tab_n, hipStream_t st);
+// resident 256-lane workgroups per CU of the closed-form rollout kernel
+int nak_rollout_blocks_per_cu();
 hipError_t launch_observe_fields(const eth::EthParams& EP, const LockBuffers& B, int64_t n,
                                  int32_t* f, hipStream_t st);
 hipError_t launch_policy(int32_t policy, int unit, const double* obs, int64_t n,

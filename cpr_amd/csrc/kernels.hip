@@ -16,6 +16,8 @@
 #include "../../include/cpr_hip.h"
 #include "kernels.h"
 #include "nakamoto_lane.h"
+#include "kernels_lock.h"
+#include "nak_rollout.h"
 #include "summary.h"
 
 #pragma clang fp contract(off)
@@ -110,9 +112,6 @@ __device__ inline CPR_AI int64_t nak_next_episode(unsigned long long* next, int6
   base = __shfl(base, leader);
   return nthreads + (int64_t)base + lane;
 }
-
-// lane status bits whose episodes the closed form cannot vouch for
-constexpr uint32_t kInexact = ST_OVERLAP | ST_DEEP_FORK | ST_TIE_UNRESOLVED | ST_STALE_TIME;
 
 // POL: nakamoto_ssz policy fixed at compile time (P_HONEST .. P_SM1; these kernels never
 // run the abstract-gamma mode), or -1 for P.policy (and P.abstract_g)
@@ -238,63 +237,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ARR == 0
 
 // ---- lockstep gym lanes (engine.reset / engine.step over n lanes)
 
-struct LockLane {
-  NakLane L;
-  uint64_t ep;
-  int64_t steps;
-  double last_ra;
-  int32_t live;
-  int32_t exact;  // 1 + the exact-engine slot this lane runs on, 0 = the closed form
-};
+// LockLane, kInexact: nak_rollout.h
 
-// nakamoto_ssz action (0 Adopt .. 3 Wait) -> the Nakamoto-mode Ethereum lane's action index
-// (eth::lane_action's mapping)
-__device__ inline int32_t nak_to_eth_action(int32_t a) {
-  constexpr int32_t map[4] = {eth::A_ADOPT_DISCARD, eth::A_OVERRIDE, eth::A_MATCH, eth::A_WAIT};
-  return map[a & 3] * 4;
-}
-
-__device__ inline LaneMem lock_mem(const NakParams& P, const LockBuffers& B, int64_t i, int64_t n) {
-  LaneMem M;
-  M.ring = B.ring + i;
-  M.ring_stride = n;
-  M.spill = B.spill + i * P.cap;  // per lane, contiguous, as the fused kernel's
-  M.spill_stride = 1;
-  M.cap = P.cap;
-  M.replay = ReplayMem::at(B.replay + i * REPLAY_BYTES);
-  return M;
-}
-
-__device__ inline void write_obs_fields(int32_t h, int32_t a, int32_t d, int32_t ev, int unit,
-                                        const double* tab_nn, const double* tab_sg,
-                                        int32_t tab_n, double* o) {
-  if (unit) {
-    // ssz_tools.ml:29-40; host-tabulated (libm) for |x| < tab_n
-    o[0] = h < tab_n ? tab_nn[h] : 2.0 / 3.141592653589793 * atan((double)h / 1.0);
-    o[1] = a < tab_n ? tab_nn[a] : 2.0 / 3.141592653589793 * atan((double)a / 1.0);
-    o[2] = (d > -tab_n && d < tab_n) ? tab_sg[d + tab_n]
-                                     : 0.5 + (1.0 / 3.141592653589793 * atan((double)d / 1.0));
-    o[3] = (double)ev / 1.0;
-  } else {
-    o[0] = (double)h;
-    o[1] = (double)a;
-    o[2] = (double)d;
-    o[3] = (double)ev;
-  }
-}
-
-__device__ inline void write_obs(const NakLane& L, int unit, const double* tab_nn,
-                                 const double* tab_sg, int32_t tab_n, double* o) {
-  int32_t h, a, d, ev;
-  L.observe(&h, &a, &d, &ev);
-  write_obs_fields(h, a, d, ev, unit, tab_nn, tab_sg, tab_n, o);
-}
-
-// a lockstep lane's slot on the exact event engine (k_lock_exact)
-__device__ inline eth::EthMem lock_exact_mem(const eth::EthParams& EP, const LockBuffers& B,
-                                             int32_t slot) {
-  return eth::eth_mem_at(B.emem + (int64_t)slot * B.elane_bytes, EP.cap_b, EP.cap_e, EP.n);
-}
+// nak_to_eth_action, lock_mem, write_obs, lock_exact_mem: kernels_lock.h
 
 __global__ __launch_bounds__(kBlock) void k_reset(NakParams P, eth::EthParams EP, uint64_t seed,
                                                    LockBuffers B, int64_t n, const uint8_t* mask,

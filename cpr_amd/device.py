@@ -330,8 +330,11 @@ class Batch:
         return out
 
     def rollout(self, n_steps, outputs=False, summary=None, device_outputs=None):
-        """Device rollout (cpr_rollout): every lane takes n_steps steps with the batch
-        policy, auto-resetting finished episodes. ``outputs=True`` returns host arrays
+        """Device rollout (cpr_rollout; Nakamoto, Ethereum, B_k and Tailstorm batches with
+        n_lanes > 0): every lane takes n_steps steps with the batch policy, auto-resetting
+        finished episodes at episode id + n_lanes. A first call without reset() starts lane
+        i at episode i; later calls, step() and reset() continue from the lanes' state.
+        ``outputs=True`` returns host arrays
         obs [n_steps, n_lanes, obs_len], reward [n_steps, n_lanes], done [n_steps, n_lanes];
         ``device_outputs=(obs_ptr, reward_ptr, done_ptr)`` writes to caller-owned device
         memory instead. Returns the summary (and the arrays if requested)."""

@@ -439,7 +439,8 @@ int cpr_step(cpr_batch* b, const int32_t* actions, double* obs, double* reward,
  * B_k the 8 bk_ssz fields (bk_ssz.ml:22-34) */
 int cpr_observe_fields(cpr_batch* b, int32_t* fields);
 
-/* Lockstep rollout on the device (B_k): every one of cfg->n_lanes lanes takes n_steps
+/* Lockstep rollout on the device (Nakamoto, Ethereum, B_k, Tailstorm; CPR_MODE_GYM batches
+ * with n_lanes > 0): every one of cfg->n_lanes lanes takes n_steps
  * steps with the batch policy (cfg->policy, built-in or table) evaluated on the device;
  * a lane whose episode ends restarts at episode id (previous id + n_lanes), like a gym
  * VecEnv auto-reset (the observation written at a done step is the new episode's first).
@@ -450,6 +451,12 @@ int cpr_observe_fields(cpr_batch* b, int32_t* fields);
  *   pointers (staged through library-owned device buffers).
  * summary (host, accumulated): steps / activations of the whole rollout, the other fields
  * over the episodes that finished in it. Synchronous; cpr_last_launch times the kernel.
+ * Nakamoto: the closed-form lane on CPR_NET_SELFISH_MINING and CPR_NET_ABSTRACT_GAMMA with
+ * the built-in policies and CPR_POLICY_TABLE (CPR_POLICY_RANDOM: CPR_E_UNSUPPORTED); a lane
+ * whose step sets CPR_ST_LOCKSTEP_INEXACT bits continues on the exact engine as under
+ * cpr_step (cpr_lockstep_coverage) until its episode ends, in further passes of the same
+ * call: cpr_last_launch covers all of them, and more than n_steps + 1 rounds of passes is
+ * CPR_E_STATE. cpr_step / cpr_reset may follow a rollout and the other way round.
  * Replaces SB3 SubprocVecEnv rollouts over cpr_gym envs (experiments/train/ppo.py:278-285). */
 int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint8_t* done,
                 int outputs_on_device, cpr_summary* summary);

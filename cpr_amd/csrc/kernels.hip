@@ -128,10 +128,10 @@ __device__ inline CPR_AI int64_t nak_next_episode(unsigned long long* next, int6
 // LZ: lazy clock (REC = 0 only; 1 at ARR = 0, 2 with the deferred races TT = 2)
 template <int MODE, class Src, int POL, int REC = 1, int ARR = -1, int TT = 0, int LZ = 0>
 #ifndef CPR_G0_WAVES
-#define CPR_G0_WAVES 8  // the gamma = 0 kernel: 61 VGPRs fit 8 waves/SIMD (7 unasked)
+#define CPR_G0_WAVES 8  // the gamma = 0 kernels: 56 VGPRs fit 8 waves/SIMD
 #endif
 #ifndef CPR_TT_WAVES
-#define CPR_TT_WAVES 5  // the d = 2 tie-rule kernels (96 VGPRs)
+#define CPR_TT_WAVES 5  // the d = 2 tie-rule kernels (93-95 VGPRs)
 #endif
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ARR == 0 ? CPR_G0_WAVES : (TT ? CPR_TT_WAVES : 4)))) void k_run_episodes(
     NakParams P, Src src, int64_t n_eps, int64_t activations,
@@ -169,6 +169,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ARR == 0
   M.cap = P.cap;
   M.replay = ReplayMem::at(replay + tid * REPLAY_BYTES);
   M.times = REC != 0;
+  M.d2 = TT != 0;
   if (!REC) recs = nullptr;
   if (TT == 2) {
     // summary-only: the ring holds no block times; each wave's race list takes its share
@@ -462,8 +463,11 @@ using ListFn = void (*)(NakParams, ListSource, int64_t, int64_t, double*, uint8_
 template <int POL>
 static RunFn gym_run_fn(const NakParams& P, bool recs, bool defer, ListFn* second) {
   if (recs) return k_run_episodes<CPR_MODE_GYM, SeedSource, POL, 1, -1>;
+  // (TT = 1 at gamma = 0, where no race is ever run: only its d = 2, so that the defender
+  // draw is a shift and the masks are 32-bit)
   if (!P.arrive && lazy_clock_ok(P) && CPR_LAZY_CLOCK)
-    return k_run_episodes<CPR_MODE_GYM, SeedSource, POL, 0, 0, 0, 1>;
+    return P.d == 2 ? k_run_episodes<CPR_MODE_GYM, SeedSource, POL, 0, 0, 1, 1>
+                    : k_run_episodes<CPR_MODE_GYM, SeedSource, POL, 0, 0, 0, 1>;
   if (!P.arrive) return k_run_episodes<CPR_MODE_GYM, SeedSource, POL, 0, 0>;
   if (P.d != 2) return k_run_episodes<CPR_MODE_GYM, SeedSource, POL, 0, 1>;
   if (!defer) return k_run_episodes<CPR_MODE_GYM, SeedSource, POL, 0, 1, 1>;

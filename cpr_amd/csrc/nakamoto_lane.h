@@ -91,6 +91,10 @@ struct LaneMem {
   uint32_t* rep = nullptr;
   int32_t lane = 0;
   int32_t wave = 1;  // lanes that share the list (WAVE in the kernels; the host tests emulate more)
+  // the kernel runs two defenders only (a compile-time true in the d = 2 kernels): the
+  // defender masks (onA, the race masks) then live in their low words and the lane keeps
+  // them there, so their 64-bit shifts, compares and selects in pairs become 32-bit ones
+  bool d2 = false;
 };
 
 // deferred races: queue entries per lane of a wave (the list is the wave's: 64 times this)
@@ -135,14 +139,24 @@ struct BRef {
   double tm;     // mining time = Simulator.timestamp for these networks (simulator.ml:14-21)
 };
 
+// c ? a : b over values already computed, which the compiler emits as a select from the
+// start. A conditional whose arm is a member access or another conditional starts as a
+// branch instead; once the lane is inlined, the branches on one condition (Adopt, the
+// miner) are merged into a single divergent region, whose many merged values are not turned
+// back into selects: each then costs a copy on either side (apply's region was 11 v_mov)
+template <class T>
+__host__ __device__ inline CPR_AI T pick(bool c, T a, T b) {
+  return c ? a : b;
+}
+
 // dst := c ? src : dst, field by field (a whole-struct conditional copy would make the
 // compiler select between the two objects' addresses and put them in scratch memory)
 __host__ __device__ inline CPR_AI void sel(BRef& dst, bool c, const BRef& src) {
-  dst.h = c ? src.h : dst.h;
-  dst.ra = c ? src.ra : dst.ra;
-  dst.k = c ? src.k : dst.k;
-  dst.fork = c ? src.fork : dst.fork;
-  dst.tm = c ? src.tm : dst.tm;
+  dst.h = pick(c, src.h, dst.h);
+  dst.ra = pick(c, src.ra, dst.ra);
+  dst.k = pick(c, src.k, dst.k);
+  dst.fork = pick(c, src.fork, dst.fork);
+  dst.tm = pick(c, src.tm, dst.tm);
 }
 
 struct NakParams {
@@ -176,6 +190,11 @@ inline uint64_t lazy_threshold(const NakParams& P) {
   return (uint64_t)std::floor(std::exp(-2.5 * P.delta / P.ev) * 9007199254740992.0);
 }
 
+// the skip test's threshold: the top 27 bits of the 53-bit u_lazy, beside the top 27 bits
+// of the uniform (w2 >> 5). uh < lazy_hi(u_lazy) implies U < u_lazy, so the high-word test
+// skips only what the full test skips; it enters the exact check for at most 2^-27 more
+inline __host__ __device__ uint32_t lazy_hi(uint64_t u_lazy) { return (uint32_t)(u_lazy >> 26); }
+
 // the lazy clock (NakLane LZ) is exact when a delay above 2 delta cannot overlap anywhere in
 // the episode: ulp(t) <= delta / 4 for every reachable clock t (each delay is at most
 // 53 ln 2 ev < 40 ev, or +inf, which the lane handles apart), and max_steps alone ends it
@@ -187,9 +206,12 @@ inline bool lazy_clock_ok(const NakParams& P) {
   if (P.max_steps <= 0 || P.max_steps > (1ll << 14)) return false;
   const double tmax = ((double)P.max_steps + 2.0) * P.ev * 40.0;
   if (!(std::ldexp(1.0, std::ilogb(tmax) - 52) <= P.delta / 4.0)) return false;
-  // delta > ~14.7 ev puts the threshold at 0: no uniform can skip the check, and the lane's
-  // skip test (u - 1 >= u_lazy - 1) would wrap and skip every one of them instead
-  return lazy_threshold(P) >= 2ull;
+  // the lane's skip test reads the high words only (lazy_hi: uh - 1 >= lazy_hi - 1, unsigned).
+  // delta > ~7.48 ev puts the threshold below 2^26 and its high word at 0: the test would
+  // wrap and skip every uniform but uh = 0 instead of none. (There exp(-2.5 delta / ev) <
+  // 8e-9 of the activations could skip the check anyway: the eager kernels run.) This
+  // also covers the threshold 0 itself (delta > ~14.7 ev)
+  return lazy_hi(lazy_threshold(P)) >= 1u;
 }
 
 __host__ __device__ inline CPR_AI uint64_t all_mask(int32_t d) {
@@ -213,11 +235,17 @@ __host__ __device__ inline CPR_AI int32_t nak_policy(int32_t policy, int32_t h, 
       if (h == 2 && a == 1) return A_ADOPT;
       if (h > 0) return (a - h == 1) ? A_OVERRIDE : A_MATCH;
       return A_WAIT;
-    case P_SM1:
-      if (h > a) return A_ADOPT;
-      if (h == 1 && a == 1) return A_MATCH;
-      if (h == a - 1 && h >= 1) return A_OVERRIDE;
-      return A_WAIT;
+    case P_SM1: {
+      // as selects over the three tests: an early return for Adopt leaves a branch whose
+      // two sides the compiler then carries through apply (its adopt selects become copies
+      // in a divergent region)
+      const bool ad = h > a;
+      const bool ma = (h == 1) & (a == 1);
+      const bool ov = (h == a - 1) & (h >= 1);
+      int32_t r = ov ? A_OVERRIDE : A_WAIT;
+      r = ma ? A_MATCH : r;
+      return ad ? A_ADOPT : r;
+    }
     default: {
       const int32_t hp = h < 0 ? 0 : (h >= dim ? dim - 1 : h);
       const int32_t ap = a < 0 ? 0 : (a >= dim ? dim - 1 : a);
@@ -495,9 +523,10 @@ struct NakLane {
     const int32_t mm = above ? m : 0;
     r.h = p0.h + mm;
     r.ra = p0.ra + mm;
-    r.k = above ? K_PRIVATE : p0.k;
+    r.k = pick(above, K_PRIVATE, p0.k);
     r.fork = r.h;  // p0.fork == p0.h always (apply sets it on Adopt)
-    r.tm = above ? chain_t(M, m) : p0.tm;
+    r.tm = 0.0;  // (chain_t reads the ring and its spill: only for a block that is there)
+    if (M.times) r.tm = above ? chain_t(M, m) : p0.tm;
     return r;
   }
 
@@ -646,8 +675,12 @@ struct NakLane {
     const int32_t miner = dr.miner;
     const double tn = t + dr.dt;
     if constexpr (LZ) {
-      // u >= u_lazy, or u == 0 (unsigned wrap), or a +inf clock: the exact check
-      if ((dr.u - 1ull) >= (P.u_lazy - 1ull) || tinf) lazy_overlap_check(P, S, dr.u);
+      // the uniform's high word (w2 >> 5) against the threshold's: uh >= lazy_hi, or uh == 0
+      // (unsigned wrap; U == 0 is among these), or a +inf clock: the exact check. It is
+      // exact whenever it runs, so entering it for a few uniforms below u_lazy (those that
+      // share its high word) changes nothing; U itself is read only in there
+      const uint32_t uh = (uint32_t)(dr.u >> 26);
+      if ((uh - 1u) >= (lazy_hi(P.u_lazy) - 1u) || tinf) lazy_overlap_check(P, S, dr.u);
       if constexpr (LZ == 2) esum += lz_term(dr.u);
     } else {
       if (tn <= w_bound) {
@@ -663,29 +696,32 @@ struct NakLane {
     // deliver the pending release to the attacker's public model (strict >)
     sel(pub, pend >= 0 && p0.h + pend > pub.h, chain_ref(M, pend));
     const bool att = miner == 0;
-    if (att) {
-      int32_t m = n + 1;
-      if (m >= M.cap) {
-        status |= ST_DEEP_FORK;
-        m = M.cap - 1;
-      }
+    {
+      // the attacker's block joins the private chain (selects; only the time ring's stores
+      // need the branch)
+      const bool deep = n + 1 >= M.cap;
+      const int32_t m = pick(deep, M.cap - 1, n + 1);
       if (M.times) {
-        double* slot = M.ring + (m & (RING - 1)) * M.ring_stride;
-        if (m > RING) M.spill[(int64_t)(m - RING) * M.spill_stride] = *slot;  // evict
-        *slot = tn;
+        if (att) {
+          double* slot = M.ring + (m & (RING - 1)) * M.ring_stride;
+          if (m > RING) M.spill[(int64_t)(m - RING) * M.spill_stride] = *slot;  // evict
+          *slot = tn;
+        }
       }
-      n = m;
+      status |= pick(att & deep, (uint32_t)ST_DEEP_FORK, 0u);
+      n = pick(att, m, n);
     }
     // the defender block (its fields are meaningless when the attacker mined)
-    const bool par_a = ((onA >> ((miner - 1) & 63)) & 1ull) != 0ull;
-    b.h = (par_a ? A.h : D.h) + 1;
-    b.ra = par_a ? A.ra : D.ra;
-    b.fork = par_a ? A.fork : D.fork;
+    const bool par_a = M.d2 ? (((uint32_t)onA >> ((miner - 1) & 31)) & 1u) != 0u
+                            : ((onA >> ((miner - 1) & 63)) & 1ull) != 0ull;
+    b.h = pick(par_a, A.h, D.h) + 1;
+    b.ra = pick(par_a, A.ra, D.ra);
+    b.fork = pick(par_a, A.fork, D.fork);
     b.k = ka;
     b.tm = M.times ? tn : 0.0;
-    const bool fresh = !att && b.h > pub.h;
+    const bool fresh = !att & (b.h > pub.h);
     sel(pub, fresh, b);
-    event = att ? 0 : (fresh ? 3 : 1);
+    event = pick(att, 0, pick(fresh, 3, 1));
   }
 
   __host__ __device__ inline CPR_AI void observe(int32_t* pub_blocks, int32_t* priv_blocks,
@@ -708,26 +744,28 @@ struct NakLane {
     const int32_t hp = pub.h;
     const bool fresh = (event & 2) != 0;  // pub is this window's defender block
     const bool onch = pub.fork == hp;                // pub lies on the private chain
-    const int32_t bf = fresh ? b.h : (onch ? (b.fork < hp ? b.fork : hp) : b.fork);
-    const int32_t df = fresh ? D.fork : (onch ? (D.fork < hp ? D.fork : hp) : D.h);
-    const int32_t af = fresh ? A.fork : (onch ? (A.fork < hp ? A.fork : hp) : lca_da);
-    const int32_t target = hp + (action == A_OVERRIDE ? 1 : 0);
+    // (every choice a pick over computed values, so that none starts as a branch)
+    const auto lo = [](int32_t x, int32_t y) { return x < y ? x : y; };
+    const int32_t bf = pick(fresh, b.h, pick(onch, lo(b.fork, hp), b.fork));
+    const int32_t df = pick(fresh, D.fork, pick(onch, lo(D.fork, hp), D.h));
+    const int32_t af = pick(fresh, A.fork, pick(onch, lo(A.fork, hp), lca_da));
+    const int32_t target = hp + pick(action == A_OVERRIDE, 1, 0);
     int32_t mf = target - p0.h;
-    mf = mf < 0 ? 0 : (mf > n ? n : mf);
-    const bool newrel = relx && mf > rel;
-    rlo = newrel ? rel + 1 : rlo;
-    rhi = newrel ? mf : rhi;
-    rel = adopt ? 0 : (newrel ? mf : rel);
-    pend = relx ? mf : -1;
-    n_ba = adopt ? 0 : n;
-    n = adopt ? 0 : n;
-    b.fork = adopt ? bf : b.fork;
-    D.fork = adopt ? df : D.fork;
-    A.fork = adopt ? af : A.fork;
+    mf = pick(mf < 0, 0, lo(mf, n));
+    const bool newrel = relx & (mf > rel);
+    rlo = pick(newrel, rel + 1, rlo);
+    rhi = pick(newrel, mf, rhi);
+    rel = pick(adopt, 0, pick(newrel, mf, rel));
+    pend = pick(relx, mf, -1);
+    n_ba = pick(adopt, 0, n);
+    n = pick(adopt, 0, n);
+    b.fork = pick(adopt, bf, b.fork);
+    D.fork = pick(adopt, df, D.fork);
+    A.fork = pick(adopt, af, A.fork);
     BRef np = pub;  // value copy: the select below picks values, not field addresses
     np.fork = hp;
     sel(p0, adopt, np);
-    pub.fork = adopt ? hp : pub.fork;
+    pub.fork = pick(adopt, hp, pub.fork);
   }
 
   // deliveries of the window: the fresh defender block and the attacker's release reach
@@ -747,21 +785,23 @@ struct NakLane {
     const uint64_t all = all_mask(P.d);
     const bool dm = wminer != 0;
     const int32_t xh = p0.h + rhi;
-    const int32_t hs = onA ? A.h : D.h;
-    const int32_t lca_new = dm ? b.fork : D.fork;  // read before the race block splits this
-    const bool newA = released && (dm ? xh >= b.h : xh > hs);
+    const int32_t hs = pick(onA != 0ull, A.h, D.h);
+    const int32_t lca_new = pick(dm, b.fork, D.fork);  // read before the race block splits this
+    const bool newA = released & pick(dm, xh >= b.h, xh > hs);
     uint64_t mask = all;
     const bool abstract_g = AG >= 0 ? AG != 0 : P.abstract_g != 0;
-    if (released && dm && xh == b.h && abstract_g) {
+    const bool race = released & dm & (xh == b.h);
+    if (race && abstract_g) {
       // flagged abstract-gamma mode: each defender, the miner included, mines on the
       // released block iff its coin falls below gamma (Eyal-Sirer'14's gamma)
       mask = 0ull;
       for (int32_t j = 1; j <= P.d; ++j)
         mask |= S.link((uint32_t)k, 0u, (uint32_t)j, 1.0) < P.gamma ? 1ull << (j - 1) : 0ull;
-    } else if (TT == 2 && released && dm && xh == b.h) {
-      mask = 1ull << (2 - wminer);  // j = 3 - wminer first reached by the release
-      rw = (uint32_t)wminer | ((uint32_t)rlo << 2) | ((uint32_t)rhi << 14);
-    } else if (released && dm && xh == b.h) {
+    } else if (TT == 2) {
+      // j = 3 - wminer first reached by the release
+      mask = pick(race, (uint64_t)(4u >> (wminer & 3)), all);
+      rw = pick(race, (uint32_t)wminer | ((uint32_t)rlo << 2) | ((uint32_t)rhi << 14), rw);
+    } else if (race) {
       // race at every defender except the miner: first visible wins. One link draw per
       // (non-miner defender, released block); the defender index is per lane.
       const double tb = t + P.delta;
@@ -796,8 +836,11 @@ struct NakLane {
       }
     }
     sel(A, newA, chain_ref(M, rhi));
-    lca_da = newA ? lca_new : lca_da;
-    onA = dm ? (newA ? mask : 0ull) : (newA ? all : onA);
+    lca_da = pick(newA, lca_new, lca_da);
+    onA = pick(dm, pick(newA, mask, (uint64_t)0), pick(newA, all, onA));
+    // d = 2: the value is its own low two bits; written so, the loop-carried mask is one
+    // 32-bit register and its tests are 32-bit ones
+    if (M.d2) onA = (uint64_t)((uint32_t)onA & 3u);
     sel(D, dm, b);
     double bound = dm && P.d >= 2 ? t + P.delta : -__builtin_inf();
     if (released) {

@@ -217,6 +217,45 @@ class StepInfo(ctypes.Structure):
     ]
 
 
+POLICY_NET_MAX_DEPTH = 4
+POLICY_NET_MAX_EXTRA = 8
+TAG_POLICY = 0x60000000  # keyed-stream tag of sampled network actions (cpr_stream.h)
+
+
+class PolicyNetC(ctypes.Structure):
+    """cpr_policy_net (include/cpr_hip.h): host pointers to f32 arrays."""
+
+    _fields_ = [
+        ("n_extra", ctypes.c_int32),
+        ("extra", ctypes.c_float * POLICY_NET_MAX_EXTRA),
+        ("depth", ctypes.c_int32),
+        ("width_pi", ctypes.c_int32),
+        ("width_vf", ctypes.c_int32),
+        ("pi_w", ctypes.c_void_p * POLICY_NET_MAX_DEPTH),
+        ("pi_b", ctypes.c_void_p * POLICY_NET_MAX_DEPTH),
+        ("pi_head_w", ctypes.c_void_p),
+        ("pi_head_b", ctypes.c_void_p),
+        ("vf_w", ctypes.c_void_p * POLICY_NET_MAX_DEPTH),
+        ("vf_b", ctypes.c_void_p * POLICY_NET_MAX_DEPTH),
+        ("vf_head_w", ctypes.c_void_p),
+        ("vf_head_b", ctypes.c_void_p),
+    ]
+
+
+class RolloutNetOut(ctypes.Structure):
+    """cpr_rollout_net_out: optional step-major output buffers."""
+
+    _fields_ = [
+        ("obs0", ctypes.c_void_p),
+        ("obs", ctypes.c_void_p),
+        ("action", ctypes.c_void_p),
+        ("reward", ctypes.c_void_p),
+        ("done", ctypes.c_void_p),
+        ("logp", ctypes.c_void_p),
+        ("value", ctypes.c_void_p),
+    ]
+
+
 class CTrace(ctypes.Structure):
     _fields_ = [
         ("n_episodes", ctypes.c_int64),
@@ -331,6 +370,9 @@ EXPORTS = [
     "cpr_step",
     "cpr_observe_fields",
     "cpr_rollout",
+    "cpr_policy_net_set",
+    "cpr_policy_net_forward",
+    "cpr_rollout_net",
     "cpr_policy_actions",
     "cpr_observation_spec",
     "cpr_policy_count",
@@ -374,6 +416,11 @@ def _declare(L):
     L.cpr_step.argtypes = [vp, vp, vp, vp, vp, P(StepInfo)]
     L.cpr_observe_fields.argtypes = [vp, vp]
     L.cpr_rollout.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int, P(Summary)]
+    L.cpr_policy_net_set.argtypes = [vp, P(PolicyNetC)]
+    L.cpr_policy_net_forward.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, vp,
+                                         vp, vp, vp]
+    L.cpr_rollout_net.argtypes = [vp, ctypes.c_int64, ctypes.c_int, P(RolloutNetOut), ctypes.c_int,
+                                  P(Summary)]
     L.cpr_policy_actions.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int64, vp]
     L.cpr_observation_spec.argtypes = [vp, P(ctypes.c_int32), P(ctypes.c_int32), vp, vp]
     L.cpr_policy_count.argtypes = [ctypes.c_int32]

@@ -16,6 +16,7 @@
 #include "eth_window.h"
 #include "kernels.h"
 #include "nak_hybrid.h"
+#include "policy_net.h"
 
 using namespace cpr;
 
@@ -179,6 +180,12 @@ struct cpr_batch {
   int32_t n_exact_slots = 0;
   // cpr_rollout over the closed-form lanes: per-lane step cursor; summary + lanes-left word
   DevBuf l_cur, l_rsum;
+  // neural-network policy (cpr_policy_net_set): the weights in one device buffer and the
+  // kernel's view of them; cpr_rollout_net's lane cursors (episode step index, activations
+  // already counted, activations at the end); cpr_policy_net_forward staging
+  bool has_net = false;
+  PolNet pn;
+  DevBuf pn_w, pn_step, pn_acts0, pn_acts, pn_in, pn_out;
   bool reset_done = false;
   int32_t tab_n = 4096;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1761,6 +1768,84 @@ static LockBuffers lock_buffers(cpr_batch* b) {
   return B;
 }
 
+// the lanes' step-output buffers (l_obs, l_rew, l_done and the step infos in l_info)
+static StepBuffers step_buffers(cpr_batch* b) {
+  const int64_t n = b->cfg.n_lanes;
+  char* ib = (char*)b->l_info.p;
+  StepBuffers sb;
+  sb.obs = (double*)b->l_obs.p;
+  sb.reward = (double*)b->l_rew.p;
+  sb.done = (uint8_t*)b->l_done.p;
+  sb.era = (double*)(ib);
+  sb.erd = (double*)(ib + n * 8);
+  sb.eprog = (double*)(ib + 2 * n * 8);
+  sb.ect = (double*)(ib + 3 * n * 8);
+  sb.est = (double*)(ib + 4 * n * 8);
+  sb.esteps = (int64_t*)(ib + 5 * n * 8);
+  sb.eacts = (int64_t*)(ib + 6 * n * 8);
+  sb.hh = (int32_t*)(ib + 7 * n * 8);
+  sb.hm = (int32_t*)(ib + 7 * n * 8 + n * 4);
+  sb.status = (uint32_t*)(ib + 7 * n * 8 + 2 * n * 4);
+  return sb;
+}
+
+// The device side of one lockstep step, shared by cpr_step and cpr_rollout_net: the
+// protocol's step kernel(s) on the device actions `act`, outputs into sb, on the context's
+// stream; nothing is copied and nothing waits.
+static int launch_lock_step(cpr_batch* b, const int32_t* act, const StepBuffers& sb) {
+  const int64_t n = b->cfg.n_lanes;
+  hipStream_t st = b->ctx->stream;
+  const double* tabs = (const double*)b->tabs_dev.p;
+  if (b->is_eth)
+    HIP_TRY(launch_eth_step(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
+                            b->bk_slots.p, n, act, b->cfg.unit_observation, tabs, b->tab_n, sb,
+                            st));
+  else if (b->cfg.protocol == CPR_PROTO_BK)
+    HIP_TRY(launch_bk_step(b->BP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
+                           b->bk_slots.p, n, act, b->cfg.unit_observation, tabs, b->tab_n, sb,
+                           st));
+  else if (b->cfg.protocol == CPR_PROTO_TAILSTORM)
+    HIP_TRY(launch_ts_step(b->TP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
+                           b->bk_slots.p, n, act, b->cfg.unit_observation, tabs, b->tab_n, sb,
+                           st));
+  else
+  {
+    const LockBuffers LB = lock_buffers(b);
+    HIP_TRY(launch_step(b->P, b->cfg.seed, LB, n, act, b->cfg.unit_observation, tabs,
+                        tabs + b->tab_n, b->tab_n, sb, st));
+    HIP_TRY(launch_lock_exact(b->NEP, b->cfg.seed, LB, n, act, b->cfg.unit_observation, tabs,
+                              tabs + b->tab_n, b->tab_n, sb, st));
+  }
+  return CPR_OK;
+}
+
+// The device side of a reset, shared by cpr_reset and cpr_rollout_net: the protocol's reset
+// kernel with a device mask and device episode ids (either may be null), every lane's
+// current observation into obs (device).
+static int launch_lock_reset(cpr_batch* b, const uint8_t* dmask, const uint64_t* deps,
+                             double* obs) {
+  const int64_t n = b->cfg.n_lanes;
+  hipStream_t st = b->ctx->stream;
+  const double* tabs = (const double*)b->tabs_dev.p;
+  if (b->is_eth)
+    HIP_TRY(launch_eth_reset(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
+                             b->bk_slots.p, n, dmask, deps, b->cfg.unit_observation, tabs,
+                             b->tab_n, obs, st));
+  else if (b->cfg.protocol == CPR_PROTO_BK)
+    HIP_TRY(launch_bk_reset(b->BP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
+                            b->bk_slots.p, n, dmask, deps, b->cfg.unit_observation, tabs,
+                            b->tab_n, obs, st));
+  else if (b->cfg.protocol == CPR_PROTO_TAILSTORM)
+    HIP_TRY(launch_ts_reset(b->TP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
+                            b->bk_slots.p, n, dmask, deps, b->cfg.unit_observation, tabs,
+                            b->tab_n, obs, st));
+  else
+    HIP_TRY(launch_reset(b->P, b->NEP, b->cfg.seed, lock_buffers(b), n, dmask, deps,
+                         b->cfg.unit_observation, tabs, tabs + b->tab_n, b->tab_n,
+                         obs, st));
+  return CPR_OK;
+}
+
 int cpr_reset(cpr_batch* b, const uint8_t* mask, const uint64_t* eps, double* obs) {
   if (!b || !obs) return fail(CPR_E_INVALID_ARG, "NULL argument");
   if (b->cfg.protocol == CPR_PROTO_FC16)
@@ -1784,24 +1869,9 @@ int cpr_reset(cpr_batch* b, const uint8_t* mask, const uint64_t* eps, double* ob
     HIP_TRY(hipMemcpyAsync(b->l_eps.p, eps, (size_t)n * 8, hipMemcpyHostToDevice, st));
     deps = (const uint64_t*)b->l_eps.p;
   }
-  const double* tabs = (const double*)b->tabs_dev.p;
   const int ol = obs_len_of(b->cfg);
-  if (b->is_eth)
-    HIP_TRY(launch_eth_reset(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
-                             b->bk_slots.p, n, dmask, deps, b->cfg.unit_observation, tabs,
-                             b->tab_n, (double*)b->l_obs.p, st));
-  else if (b->cfg.protocol == CPR_PROTO_BK)
-    HIP_TRY(launch_bk_reset(b->BP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
-                            b->bk_slots.p, n, dmask, deps, b->cfg.unit_observation, tabs,
-                            b->tab_n, (double*)b->l_obs.p, st));
-  else if (b->cfg.protocol == CPR_PROTO_TAILSTORM)
-    HIP_TRY(launch_ts_reset(b->TP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
-                            b->bk_slots.p, n, dmask, deps, b->cfg.unit_observation, tabs,
-                            b->tab_n, (double*)b->l_obs.p, st));
-  else
-    HIP_TRY(launch_reset(b->P, b->NEP, b->cfg.seed, lock_buffers(b), n, dmask, deps,
-                         b->cfg.unit_observation, tabs, tabs + b->tab_n, b->tab_n,
-                         (double*)b->l_obs.p, st));
+  rc = launch_lock_reset(b, dmask, deps, (double*)b->l_obs.p);
+  if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(obs, b->l_obs.p, (size_t)n * ol * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   b->reset_done = true;
@@ -1821,42 +1891,9 @@ int cpr_step(cpr_batch* b, const int32_t* actions, double* obs, double* reward, 
   HIP_TRY(hipSetDevice(b->ctx->device));
   hipStream_t st = b->ctx->stream;
   HIP_TRY(hipMemcpyAsync(b->l_act.p, actions, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  char* ib = (char*)b->l_info.p;
-  StepBuffers sb;
-  sb.obs = (double*)b->l_obs.p;
-  sb.reward = (double*)b->l_rew.p;
-  sb.done = (uint8_t*)b->l_done.p;
-  sb.era = (double*)(ib);
-  sb.erd = (double*)(ib + n * 8);
-  sb.eprog = (double*)(ib + 2 * n * 8);
-  sb.ect = (double*)(ib + 3 * n * 8);
-  sb.est = (double*)(ib + 4 * n * 8);
-  sb.esteps = (int64_t*)(ib + 5 * n * 8);
-  sb.eacts = (int64_t*)(ib + 6 * n * 8);
-  sb.hh = (int32_t*)(ib + 7 * n * 8);
-  sb.hm = (int32_t*)(ib + 7 * n * 8 + n * 4);
-  sb.status = (uint32_t*)(ib + 7 * n * 8 + 2 * n * 4);
-  const double* tabs = (const double*)b->tabs_dev.p;
-  if (b->is_eth)
-    HIP_TRY(launch_eth_step(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
-                            b->bk_slots.p, n, (const int32_t*)b->l_act.p,
-                            b->cfg.unit_observation, tabs, b->tab_n, sb, st));
-  else if (b->cfg.protocol == CPR_PROTO_BK)
-    HIP_TRY(launch_bk_step(b->BP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
-                           b->bk_slots.p, n, (const int32_t*)b->l_act.p,
-                           b->cfg.unit_observation, tabs, b->tab_n, sb, st));
-  else if (b->cfg.protocol == CPR_PROTO_TAILSTORM)
-    HIP_TRY(launch_ts_step(b->TP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
-                           b->bk_slots.p, n, (const int32_t*)b->l_act.p,
-                           b->cfg.unit_observation, tabs, b->tab_n, sb, st));
-  else
-  {
-    const LockBuffers LB = lock_buffers(b);
-    HIP_TRY(launch_step(b->P, b->cfg.seed, LB, n, (const int32_t*)b->l_act.p,
-                        b->cfg.unit_observation, tabs, tabs + b->tab_n, b->tab_n, sb, st));
-    HIP_TRY(launch_lock_exact(b->NEP, b->cfg.seed, LB, n, (const int32_t*)b->l_act.p,
-                              b->cfg.unit_observation, tabs, tabs + b->tab_n, b->tab_n, sb, st));
-  }
+  const StepBuffers sb = step_buffers(b);
+  int rc = launch_lock_step(b, (const int32_t*)b->l_act.p, sb);
+  if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(obs, sb.obs, (size_t)n * ol * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(reward, sb.reward, (size_t)n * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(done, sb.done, (size_t)n, hipMemcpyDeviceToHost, st));
@@ -2262,6 +2299,305 @@ int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint
                      (is_nak ? nak_rollout_blocks_per_cu() : b->is_eth ? eth_blocks_per_cu()
                                 : (b->cfg.protocol == CPR_PROTO_TAILSTORM ? ts_blocks_per_cu()
                                                                           : bk_blocks_per_cu()));
+  summary->episodes += s.episodes;
+  summary->steps += s.steps;
+  summary->activations += s.activations;
+  summary->reward_attacker_fx += s.reward_attacker_fx;
+  summary->reward_defender_fx += s.reward_defender_fx;
+  summary->progress_fx += s.progress_fx;
+  summary->rel_revenue_fx += s.rel_revenue_fx;
+  summary->rel_revenue_sq_fx += s.rel_revenue_sq_fx;
+  summary->orphans += s.orphans;
+  summary->status_tie += s.status_tie;
+  summary->status_overlap += s.status_overlap;
+  summary->status_other += s.status_other;
+  summary->invalid += s.invalid;
+  for (int i = 0; i < CPR_HIST_BINS; i++) summary->hist[i] += s.hist[i];
+  return CPR_OK;
+}
+
+// ---------------------------------------------------------------- neural-network policies
+
+int cpr_policy_net_set(cpr_batch* b, const cpr_policy_net* net) {
+  if (!b || !net) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (b->cfg.protocol == CPR_PROTO_FC16)
+    return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
+  if (b->cfg.n_lanes <= 0 || b->cfg.mode != CPR_MODE_GYM)
+    return fail(CPR_E_UNSUPPORTED, "a policy network needs lockstep lanes (CPR_MODE_GYM, "
+                                   "cfg.n_lanes > 0)");
+  if (net->depth < 1 || net->depth > kPolMaxDepth)
+    return fail(CPR_E_INVALID_ARG, "policy net: depth must be in 1..4");
+  for (int32_t w : {net->width_pi, net->width_vf})
+    if (w < 16 || w > kPolMaxWidth || w % 16 != 0)
+      return fail(CPR_E_INVALID_ARG, "policy net: width must be a multiple of 16 in [16, 512]");
+  if (net->n_extra < 0 || net->n_extra > kPolMaxExtra)
+    return fail(CPR_E_INVALID_ARG, "policy net: n_extra must be in 0..8");
+  for (int i = 0; i < net->n_extra; i++)
+    if (!std::isfinite(net->extra[i]))
+      return fail(CPR_E_INVALID_ARG, "policy net: non-finite extra feature");
+  int32_t ol = 0, na = 0;
+  int rc = cpr_observation_spec(b, &ol, &na, nullptr, nullptr);
+  if (rc) return rc;
+  if (ol + net->n_extra > kPolInStride || na > kPolMaxActions)
+    return fail(CPR_E_UNSUPPORTED, "policy net: input or action head wider than the kernel's tile");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  // the LDS a workgroup's tile needs, checked here so that no launch can exceed the device
+  const int64_t lds = policy_lds_bytes(net->depth, net->width_pi, net->width_vf);
+  if (lds > policy_lds_limit())
+    return fail(CPR_E_UNSUPPORTED,
+                "policy net: depth " + std::to_string(net->depth) + ", width " +
+                    std::to_string(std::max(net->width_pi, net->width_vf)) + " needs " +
+                    std::to_string(lds) + " B of LDS per workgroup, the device has " +
+                    std::to_string(policy_lds_limit()));
+  // one host image of every array, then one upload; offsets in floats
+  struct Arr {
+    const float* src;
+    int64_t count;
+    const float** dst;
+  };
+  PolNet N = {};
+  N.obs_len = ol;
+  N.n_extra = net->n_extra;
+  N.depth = net->depth;
+  N.n_actions = na;
+  N.width_pi = net->width_pi;
+  N.width_vf = net->width_vf;
+  for (int i = 0; i < net->n_extra; i++) N.extra[i] = net->extra[i];
+  std::vector<Arr> arrs;
+  for (int trunk = 0; trunk < 2; trunk++) {
+    PolLayer* Ls = trunk == 0 ? N.pi : N.vf;
+    const int32_t width = trunk == 0 ? net->width_pi : net->width_vf;
+    const float* const* ws = trunk == 0 ? net->pi_w : net->vf_w;
+    const float* const* bs = trunk == 0 ? net->pi_b : net->vf_b;
+    for (int l = 0; l <= net->depth; l++) {
+      const bool head = l == net->depth;
+      Ls[l].n_in = l == 0 ? ol + net->n_extra : width;
+      Ls[l].n_out = head ? (trunk == 0 ? na : 1) : width;
+      const float* w = head ? (trunk == 0 ? net->pi_head_w : net->vf_head_w) : ws[l];
+      const float* bias = head ? (trunk == 0 ? net->pi_head_b : net->vf_head_b) : bs[l];
+      if (!w || !bias) return fail(CPR_E_INVALID_ARG, "policy net: NULL weight or bias array");
+      arrs.push_back({w, (int64_t)Ls[l].n_in * Ls[l].n_out, &Ls[l].W});
+      arrs.push_back({bias, (int64_t)Ls[l].n_out, &Ls[l].b});
+    }
+  }
+  std::vector<float> host;
+  std::vector<int64_t> offs;
+  for (const Arr& a : arrs) {
+    offs.push_back((int64_t)host.size());
+    for (int64_t i = 0; i < a.count; i++) {
+      if (!std::isfinite(a.src[i]))
+        return fail(CPR_E_INVALID_ARG, "policy net: non-finite weight or bias");
+      host.push_back(a.src[i]);
+    }
+    while (host.size() % 4) host.push_back(0.f);
+  }
+  // a forward of the previous network may still be reading the buffer
+  HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+  HIP_TRY(b->pn_w.ensure(host.size() * sizeof(float)));
+  HIP_TRY(hipMemcpy(b->pn_w.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+  for (size_t i = 0; i < arrs.size(); i++) *arrs[i].dst = (const float*)b->pn_w.p + offs[i];
+  b->pn = N;
+  b->has_net = true;
+  return CPR_OK;
+}
+
+int cpr_policy_net_forward(cpr_batch* b, const double* obs, int64_t n, int deterministic,
+                           uint64_t episode0, int32_t* actions, double* logp, double* value,
+                           float* logits) {
+  if (!b || !obs) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
+  if (n < 1) return fail(CPR_E_INVALID_ARG, "policy net forward: n must be >= 1");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  hipStream_t st = b->ctx->stream;
+  const int ol = b->pn.obs_len, na = b->pn.n_actions;
+  const size_t o_act = 0, o_logp = align256((size_t)n * 4), o_val = o_logp + align256((size_t)n * 8),
+               o_lg = o_val + align256((size_t)n * 8), total = o_lg + (size_t)n * na * 4;
+  HIP_TRY(b->pn_in.ensure((size_t)n * ol * 8));
+  HIP_TRY(b->pn_out.ensure(total));
+  char* ob = (char*)b->pn_out.p;
+  HIP_TRY(hipMemcpyAsync(b->pn_in.p, obs, (size_t)n * ol * 8, hipMemcpyHostToDevice, st));
+  PolIO io = {};
+  io.obs = (const double*)b->pn_in.p;
+  io.n = n;
+  io.deterministic = deterministic ? 1 : 0;
+  io.seed = b->cfg.seed;
+  io.episode0 = episode0;
+  io.action = actions ? (int32_t*)(ob + o_act) : nullptr;
+  io.logp = logp ? (double*)(ob + o_logp) : nullptr;
+  io.value = value ? (double*)(ob + o_val) : nullptr;
+  io.logits = logits ? (float*)(ob + o_lg) : nullptr;
+  if (!b->ev0) {
+    HIP_TRY(hipEventCreate(&b->ev0));
+    HIP_TRY(hipEventCreate(&b->ev1));
+  }
+  HIP_TRY(hipEventRecord(b->ev0, st));
+  HIP_TRY(launch_policy_forward(b->pn, io, st));
+  HIP_TRY(hipEventRecord(b->ev1, st));
+  if (actions) HIP_TRY(hipMemcpyAsync(actions, io.action, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  if (logp) HIP_TRY(hipMemcpyAsync(logp, io.logp, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  if (value) HIP_TRY(hipMemcpyAsync(value, io.value, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  if (logits)
+    HIP_TRY(hipMemcpyAsync(logits, io.logits, (size_t)n * na * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0.f;  // cpr_last_launch: the forward kernel alone
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+  b->last_ms = ms;
+  b->last_acts = 0;
+  b->async_launch = false;
+  return CPR_OK;
+}
+
+// where the lanes stand, from the protocol's own lane state
+static int launch_lane_cursor(cpr_batch* b, const LaneCursor& c) {
+  const int64_t n = b->cfg.n_lanes;
+  hipStream_t st = b->ctx->stream;
+  if (b->is_eth)
+    HIP_TRY(launch_eth_cursor(b->bk_slots.p, n, c, st));
+  else if (b->cfg.protocol == CPR_PROTO_BK)
+    HIP_TRY(launch_bk_cursor(b->bk_slots.p, n, c, st));
+  else if (b->cfg.protocol == CPR_PROTO_TAILSTORM)
+    HIP_TRY(launch_ts_cursor(b->bk_slots.p, n, c, st));
+  else
+    HIP_TRY(launch_lock_cursor(lock_buffers(b), n, c, st));
+  return CPR_OK;
+}
+
+int cpr_rollout_net(cpr_batch* b, int64_t n_steps, int deterministic,
+                    const cpr_rollout_net_out* out, int outputs_on_device,
+                    cpr_summary* summary) {
+  if (!b || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (b->cfg.protocol == CPR_PROTO_FC16)
+    return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
+  if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
+  if (n_steps <= 0) return CPR_OK;
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  int rc = ensure_lockstep(b);
+  if (rc) return rc;
+  const int64_t n = b->cfg.n_lanes;
+  const int ol = obs_len_of(b->cfg);
+  const int64_t cells = n_steps * n;
+  hipStream_t st = b->ctx->stream;
+  HIP_TRY(b->summary.ensure(sizeof(cpr_summary)));
+  HIP_TRY(hipMemsetAsync(b->summary.p, 0, sizeof(cpr_summary), st));
+  if (!b->ev0) {
+    HIP_TRY(hipEventCreate(&b->ev0));
+    HIP_TRY(hipEventCreate(&b->ev1));
+  }
+  HIP_TRY(b->pn_step.ensure((size_t)n * 8));
+  HIP_TRY(b->pn_acts0.ensure((size_t)n * 8));
+  HIP_TRY(b->pn_acts.ensure((size_t)n * 8));
+  // outputs: the caller's device buffers, or library-owned staging copied back at the end
+  cpr_rollout_net_out H = {};
+  if (out) H = *out;
+  cpr_rollout_net_out D = H;
+  struct Stage {
+    void** dev;
+    void* host;
+    size_t bytes;
+    DevBuf buf;
+  };
+  Stage stage[7] = {{(void**)&D.obs0, H.obs0, (size_t)n * ol * 8, {}},
+                    {(void**)&D.obs, H.obs, (size_t)cells * ol * 8, {}},
+                    {(void**)&D.action, H.action, (size_t)cells * 4, {}},
+                    {(void**)&D.reward, H.reward, (size_t)cells * 8, {}},
+                    {(void**)&D.done, H.done, (size_t)cells, {}},
+                    {(void**)&D.logp, H.logp, (size_t)cells * 8, {}},
+                    {(void**)&D.value, H.value, (size_t)(cells + n) * 8, {}}};
+  if (!outputs_on_device)
+    for (Stage& s : stage)
+      if (s.host) {
+        HIP_TRY(s.buf.ensure(s.bytes));
+        *s.dev = s.buf.p;
+      }
+  const StepBuffers sb = step_buffers(b);
+  HIP_TRY(hipEventRecord(b->ev0, st));
+  // a first call without a reset starts lane i at episode i (that reset's activations count,
+  // as in the built-in rollout); otherwise the reset kernel with an empty mask resets nothing
+  // and writes every lane's current observation into l_obs (cpr_rollout leaves none there)
+  const bool fresh = !b->reset_done;
+  if (!fresh) HIP_TRY(hipMemsetAsync(b->l_mask.p, 0, (size_t)n, st));
+  rc = launch_lock_reset(b, fresh ? nullptr : (const uint8_t*)b->l_mask.p, nullptr, sb.obs);
+  if (rc) return rc;
+  LaneCursor cur;
+  cur.ep = (uint64_t*)b->l_eps.p;
+  cur.steps = (int64_t*)b->pn_step.p;
+  cur.acts = (int64_t*)b->pn_acts0.p;
+  rc = launch_lane_cursor(b, cur);
+  if (rc) return rc;
+  if (fresh) HIP_TRY(hipMemsetAsync(b->pn_acts0.p, 0, (size_t)n * 8, st));
+  if (D.obs0)
+    HIP_TRY(hipMemcpyAsync(D.obs0, sb.obs, (size_t)n * ol * 8, hipMemcpyDeviceToDevice, st));
+  PolIO io = {};
+  io.n = n;
+  io.deterministic = deterministic ? 1 : 0;
+  io.seed = b->cfg.seed;
+  io.ep = cur.ep;
+  io.step = cur.steps;
+  PolCollect C = {};
+  C.reward = sb.reward;
+  C.done = sb.done;
+  C.era = sb.era;
+  C.erd = sb.erd;
+  C.eprog = sb.eprog;
+  C.esteps = sb.esteps;
+  C.eacts = sb.eacts;
+  C.hh = sb.hh;
+  C.status = sb.status;
+  C.orphans_from_progress = b->is_ev ? 1 : 0;
+  C.ep = cur.ep;
+  C.step = cur.steps;
+  C.acts0 = cur.acts;
+  C.mask = (uint8_t*)b->l_mask.p;
+  C.sum = (cpr_summary*)b->summary.p;
+  // the policy input of step t: l_obs before the first step, then where the reset kernel
+  // of step t - 1 wrote every lane's observation (the caller's obs row, or l_obs)
+  const double* in_obs = sb.obs;
+  for (int64_t t = 0; t < n_steps; ++t) {
+    int32_t* act = D.action ? D.action + t * n : (int32_t*)b->l_act.p;
+    io.obs = in_obs;
+    io.action = act;
+    io.logp = D.logp ? D.logp + t * n : nullptr;
+    io.value = D.value ? D.value + t * n : nullptr;
+    HIP_TRY(launch_policy_forward(b->pn, io, st));
+    rc = launch_lock_step(b, act, sb);
+    if (rc) return rc;
+    C.out_reward = D.reward ? D.reward + t * n : nullptr;
+    C.out_done = D.done ? D.done + t * n : nullptr;
+    HIP_TRY(launch_policy_collect(C, n, st));
+    double* next_obs = D.obs ? D.obs + t * n * ol : sb.obs;
+    rc = launch_lock_reset(b, C.mask, cur.ep, next_obs);
+    if (rc) return rc;
+    in_obs = next_obs;
+  }
+  if (D.value) {  // PPO's bootstrap: the value of the final observation
+    io.obs = in_obs;
+    io.deterministic = 1;
+    io.action = nullptr;
+    io.logp = nullptr;
+    io.value = D.value + cells;
+    HIP_TRY(launch_policy_forward(b->pn, io, st));
+  }
+  // activations of the episodes still running
+  LaneCursor end = cur;
+  end.acts = (int64_t*)b->pn_acts.p;
+  rc = launch_lane_cursor(b, end);
+  if (rc) return rc;
+  HIP_TRY(launch_policy_tail(end.acts, cur.acts, n, C.sum, st));
+  HIP_TRY(hipEventRecord(b->ev1, st));
+  cpr_summary s;
+  HIP_TRY(hipMemcpyAsync(&s, b->summary.p, sizeof(s), hipMemcpyDeviceToHost, st));
+  if (!outputs_on_device)
+    for (Stage& g : stage)
+      if (g.host) HIP_TRY(hipMemcpyAsync(g.host, *g.dev, g.bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+  b->last_ms = ms;
+  b->last_acts = s.activations;
+  b->async_launch = false;
+  b->reset_done = true;
+  b->last_lanes = n;
+  b->last_resident = n;
   summary->episodes += s.episodes;
   summary->steps += s.steps;
   summary->activations += s.activations;

@@ -30,6 +30,9 @@ constexpr uint32_t TAG_MSG = 0x30000000u;
 // random attacker actions (cpr_protocols.ml:658-782, Random.int A.Action.n): decision i of
 // an episode draws word 0 of block (i, TAG_RAND) (oracle/src/keyed_stream.h rand_action)
 constexpr uint32_t TAG_RAND = 0x50000000u;
+// sampled actions of a neural-network policy (kernels_policy.hip): the step with episode
+// step index i draws u53(w0, w1) of block (i, TAG_POLICY)
+constexpr uint32_t TAG_POLICY = 0x60000000u;
 
 struct Words4 {
   uint32_t w0, w1, w2, w3;

@@ -148,6 +148,30 @@ hipError_t launch_stream_fill(uint64_t seed, uint64_t ep, uint32_t idx0, uint32_
                               uint32_t* out, double* exp_out, hipStream_t st);
 size_t lock_lane_bytes();
 
+// Where every lockstep lane stands (cpr_rollout_net): its episode id, the steps and the
+// activations of that episode so far (device arrays of n). A lane never reset reports
+// episode i, 0 steps, 0 activations.
+struct LaneCursor {
+  uint64_t* ep;
+  int64_t* steps;
+  int64_t* acts;
+};
+// the event-engine slots (EthSlot, BkSlot, TsSlot: lane L with steps / c_act, ep, live)
+template <class Slot>
+__global__ void k_slot_cursor(const Slot* slots, int64_t n, LaneCursor c) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool live = slots[i].live != 0;
+  c.ep[i] = live ? slots[i].ep : (uint64_t)i;
+  c.steps[i] = live ? (int64_t)slots[i].L.steps : 0;
+  c.acts[i] = live ? (int64_t)slots[i].L.c_act : 0;
+}
+hipError_t launch_lock_cursor(const LockBuffers& B, int64_t n, const LaneCursor& c,
+                              hipStream_t st);
+hipError_t launch_eth_cursor(const void* slots, int64_t n, const LaneCursor& c, hipStream_t st);
+hipError_t launch_bk_cursor(const void* slots, int64_t n, const LaneCursor& c, hipStream_t st);
+hipError_t launch_ts_cursor(const void* slots, int64_t n, const LaneCursor& c, hipStream_t st);
+
 // Per-node outputs of the event-engine episode kernels (cpr_node_outputs): a second
 // per-lane region (activations per node, per-block reward arrays) and the [episode][node]
 // output rows; mem == nullptr disables them

@@ -786,6 +786,12 @@ hipError_t launch_bk_observe_fields(const bk::BkParams& P, uint8_t* mem, int64_t
   return hipGetLastError();
 }
 
+hipError_t launch_bk_cursor(const void* slots, int64_t n, const LaneCursor& c, hipStream_t st) {
+  hipLaunchKernelGGL(k_slot_cursor<BkSlot>, dim3(grid_of(n)), dim3(kBlock), 0, st,
+                     (const BkSlot*)slots, n, c);
+  return hipGetLastError();
+}
+
 hipError_t launch_bk_policy(const bk::BkParams& P, int unit, const double* obs, int64_t n,
                             int32_t* actions, hipStream_t st) {
   hipLaunchKernelGGL(k_bk_policy, dim3(grid_of(n)), dim3(kBlock), 0, st, P, unit, obs, n,

@@ -810,6 +810,12 @@ hipError_t launch_eth_observe_fields(const eth::EthParams& P, uint8_t* mem, int6
   return hipGetLastError();
 }
 
+hipError_t launch_eth_cursor(const void* slots, int64_t n, const LaneCursor& c, hipStream_t st) {
+  hipLaunchKernelGGL(k_slot_cursor<EthSlot>, dim3(eth_grid_of(n)), dim3(kBlock), 0, st,
+                     (const EthSlot*)slots, n, c);
+  return hipGetLastError();
+}
+
 hipError_t launch_eth_policy(int32_t policy, int unit, const double* obs, int64_t n,
                              const uint8_t* table, int32_t dim, int32_t* actions,
                              hipStream_t st) {

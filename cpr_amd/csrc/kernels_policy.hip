@@ -1,0 +1,294 @@
+// gfx950 kernels of the neural-network policy (policy_net.h):
+//   k_policy_forward   the whole actor-critic MLP for a tile of rows per workgroup, on the
+//                      f32-input MFMA (v_mfma_f32_16x16x4_f32: f32 in, f32 accumulate), then
+//                      argmax / keyed sampling, log-probability and value per row in f64
+//   k_policy_collect   per-step bookkeeping of cpr_rollout_net: step-major outputs, summary
+//                      of finished episodes, lane cursors, reset mask
+//   k_policy_tail      activations of the episodes still running when the rollout ends
+//   k_lock_cursor      where the Nakamoto lockstep lanes stand when a rollout begins
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "kernels.h"
+#include "nak_rollout.h"
+#include "policy_net.h"
+#include "summary.h"
+
+#pragma clang fp contract(off)
+
+namespace cpr {
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+extern __shared__ __attribute__((aligned(16))) float pol_lds[];
+
+// threads of a k_policy_forward workgroup: eight waves, two per SIMD, so that one wave's
+// barrier and LDS waits overlap the other's MFMAs
+constexpr int kPolThreads = 512;
+
+// dst[r][c] = act(sum_k src[r][k] W[c][k] + b[c]) for the workgroup's kPolRows rows.
+// src / dst are LDS tiles (src zero-filled up to the next multiple of 4 columns); W is staged
+// through `ws` in chunks of kPolNT output units x kPolKT inputs, zero beyond n_out / n_in.
+// Wave w owns the 16 output units n0 + 16 (w & 3) .. of a chunk for the 32 rows of half
+// w >> 2: two 16x16 accumulators. Operand lane maps of the 16x16x4 f32 MFMA: A[lane & 15][k = lane >> 4],
+// B[k = lane >> 4][lane & 15]; C/D column = lane & 15, row = 4 (lane >> 4) + register.
+__device__ inline void pol_layer(const float* src, int sstride, const PolLayer& Ly, float* ws,
+                                 float* dst, int dstride, bool relu) {
+  constexpr int kStage = kPolNT * kPolKT / kPolThreads;  // weights a thread stages per chunk
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3, half = tid >> 8;
+  const int K = Ly.n_in, N = Ly.n_out;
+  const int Kp = (K + 3) & ~3;
+  const int r16 = lane & 15, q = lane >> 4;
+  const int kch = (Kp + kPolKT - 1) / kPolKT;
+  const int total = ((N + kPolNT - 1) / kPolNT) * kch;
+  // chunk c = (n-chunk c / kch, k-chunk c % kch); its weights travel global -> registers ->
+  // LDS, and the loads of chunk c + 1 are in flight while chunk c is multiplied
+  float stage[kStage];
+  auto fetch = [&](int c) {
+    const int n0 = (c / kch) * kPolNT, k0 = (c % kch) * kPolKT;
+#pragma unroll
+    for (int i = 0; i < kStage; ++i) {
+      const int idx = tid + i * kPolThreads;
+      const int o = n0 + idx / kPolKT, k = k0 + idx % kPolKT;
+      stage[i] = (o < N && k < K) ? Ly.W[(int64_t)o * K + k] : 0.f;
+    }
+  };
+  fetch(0);
+  f32x4 acc[2];
+  for (int c = 0; c < total; ++c) {
+    const int n0 = (c / kch) * kPolNT, k0 = (c % kch) * kPolKT;
+    __syncthreads();  // the previous chunk is consumed; src is complete
+#pragma unroll
+    for (int i = 0; i < kStage; ++i) {
+      const int idx = tid + i * kPolThreads;
+      ws[(idx / kPolKT) * kPolWsStride + idx % kPolKT] = stage[i];
+    }
+    __syncthreads();
+    if (c + 1 < total) fetch(c + 1);
+    const bool active = n0 + wave * 16 < N;  // wave-uniform
+    if (k0 == 0) {
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb) acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (active) {
+      const float* wrow = ws + (wave * 16 + r16) * kPolWsStride + q;
+      const float* arow = src + (half * 32 + r16) * sstride + k0 + q;
+      if (Kp - k0 >= kPolKT) {
+#pragma unroll
+        for (int kk = 0; kk < kPolKT; kk += 4) {
+          const float b = wrow[kk];
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+            acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[rb * 16 * sstride + kk], b,
+                                                           acc[rb], 0, 0, 0);
+        }
+      } else {
+        for (int kk = 0; kk < Kp - k0; kk += 4) {
+          const float b = wrow[kk];
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+            acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[rb * 16 * sstride + kk], b,
+                                                           acc[rb], 0, 0, 0);
+        }
+      }
+    }
+    const int col = n0 + wave * 16 + r16;
+    if (k0 + kPolKT >= Kp && active && col < N) {  // the n-chunk's last k-chunk
+      const float bias = Ly.b[col];
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          float v = acc[rb][g] + bias;
+          if (relu) v = v < 0.f ? 0.f : v;
+          dst[(half * 32 + rb * 16 + q * 4 + g) * dstride + col] = v;
+        }
+    }
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kPolThreads) void k_policy_forward(PolNet N, PolIO io, int32_t hstride) {
+  float* xin = pol_lds;
+  float* ws = xin + kPolRows * kPolInStride;
+  float* lg = ws + kPolNT * kPolWsStride;
+  float* val = lg + kPolRows * kPolLogitStride;
+  float* h0 = val + kPolRows;
+  float* h1 = h0 + kPolRows * hstride;  // used from depth 2 on (policy_lds_bytes)
+  const int tid = (int)threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * kPolRows;
+  const int n_in = N.obs_len + N.n_extra;
+  // the input tile: f64 observation -> f32, the batch constants appended, zero beyond n_in
+  // and for rows beyond n
+  for (int idx = tid; idx < kPolRows * kPolInStride; idx += kPolThreads) {
+    const int r = idx / kPolInStride, c = idx - r * kPolInStride;
+    const int64_t row = r0 + r;
+    float v = 0.f;
+    if (row < io.n) {
+      if (c < N.obs_len)
+        v = (float)io.obs[row * N.obs_len + c];
+      else if (c < n_in)
+        v = N.extra[c - N.obs_len];
+    }
+    xin[idx] = v;
+  }
+  // (pol_layer's first barrier orders the tile before its readers)
+  for (int trunk = 0; trunk < 2; ++trunk) {
+    const PolLayer* Ls = trunk == 0 ? N.pi : N.vf;
+    const float* src = xin;
+    int sstride = kPolInStride;
+    for (int l = 0; l < N.depth; ++l) {
+      float* dst = (l & 1) ? h1 : h0;
+      pol_layer(src, sstride, Ls[l], ws, dst, hstride, true);
+      src = dst;
+      sstride = hstride;
+    }
+    if (trunk == 0)
+      pol_layer(src, sstride, Ls[N.depth], ws, lg, kPolLogitStride, false);
+    else
+      pol_layer(src, sstride, Ls[N.depth], ws, val, 1, false);
+  }
+  const int64_t row = r0 + tid;
+  if (tid >= kPolRows || row >= io.n) return;
+  const float* l = lg + tid * kPolLogitStride;
+  const int na = N.n_actions;
+  float mf = l[0];
+  int am = 0;
+  for (int i = 1; i < na; ++i)
+    if (l[i] > mf) {  // the lowest index of the maximum
+      mf = l[i];
+      am = i;
+    }
+  const double m = (double)mf;
+  double S = 0.0;
+  for (int i = 0; i < na; ++i) S += exp((double)l[i] - m);
+  int a = am;
+  if (!io.deterministic) {
+    // u of the keyed block (episode, step index, TAG_POLICY): the smallest a with
+    // u S < sum_{i <= a} e_i, the last action if rounding leaves none
+    const uint64_t ep = io.ep ? io.ep[row] : io.episode0 + (uint64_t)row;
+    const uint32_t si = io.step ? (uint32_t)io.step[row] : 0u;
+    const Words4 w = make_stream(io.seed, ep).block(si, TAG_POLICY);
+    const double uS = u53(w.w0, w.w1) * S;
+    double c = 0.0;
+    a = na - 1;
+    for (int i = 0; i < na; ++i) {
+      c += exp((double)l[i] - m);
+      if (uS < c) {
+        a = i;
+        break;
+      }
+    }
+  }
+  if (io.action) io.action[row] = a;
+  if (io.logp) io.logp[row] = ((double)l[a] - m) - log(S);
+  if (io.value) io.value[row] = (double)val[tid];
+  if (io.logits)
+    for (int i = 0; i < na; ++i) io.logits[row * na + i] = l[i];
+}
+
+__global__ __launch_bounds__(kBlock) void k_policy_collect(PolCollect C, int64_t n) {
+  __shared__ int32_t hist[CPR_HIST_BINS];
+  if (threadIdx.x < CPR_HIST_BINS) hist[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  Acc acc = {};
+  int64_t steps_all = 0, acts_all = 0;
+  if (i < n) {
+    const uint8_t d = C.done[i];
+    if (C.out_reward) C.out_reward[i] = C.reward[i];
+    if (C.out_done) C.out_done[i] = d;
+    C.mask[i] = d;
+    steps_all = 1;
+    if (d) {
+      // summary.h's fixed-point rule on the step infos of the episode's last step
+      const double ra = C.era[i], rd = C.erd[i], prog = C.eprog[i];
+      const double rel = (ra + rd) != 0.0 ? ra / (ra + rd) : 0.0;
+      const int64_t acts = C.eacts[i];
+      const int64_t hh = C.orphans_from_progress ? (int64_t)prog : (int64_t)C.hh[i];
+      acc_episode(acc, (int64_t)__builtin_rint(ra * 1048576.0),
+                  (int64_t)__builtin_rint(rd * 1048576.0),
+                  (int64_t)__builtin_rint(prog * 1048576.0), rel, hh, C.esteps[i], acts,
+                  C.status[i], hist);
+      acts_all = acts - C.acts0[i];
+      C.acts0[i] = 0;
+      C.ep[i] += (uint64_t)n;  // VecEnv auto-reset: the lane's next episode
+      C.step[i] = 0;
+    } else {
+      C.step[i] += 1;
+    }
+  }
+  // rollout totals: every step and activation (acc holds finished episodes only)
+  acc.steps = steps_all;
+  acc.activations = acts_all;
+  __syncthreads();
+  block_flush(acc, hist, C.sum);
+}
+
+__global__ __launch_bounds__(kBlock) void k_policy_tail(const int64_t* acts, const int64_t* acts0,
+                                                        int64_t n, cpr_summary* sum) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t v = wave_sum(i < n ? acts[i] - acts0[i] : 0);
+  if ((threadIdx.x & 63) == 0 && v)
+    atomicAdd((unsigned long long*)&sum->activations, (unsigned long long)v);
+}
+
+// LaneCursor of the Nakamoto lockstep lanes (closed form, or the lane's exact-engine slot)
+__global__ void k_lock_cursor(LockBuffers B, int64_t n, LaneCursor c) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const LockLane& LL = ((const LockLane*)B.lanes)[i];
+  const bool live = LL.live != 0;
+  c.ep[i] = live ? LL.ep : (uint64_t)i;
+  c.steps[i] = live ? LL.steps : 0;
+  int64_t acts = live ? (int64_t)LL.L.k : 0;
+  if (live && LL.exact) acts = ((const eth::EthLane*)B.eslots)[LL.exact - 1].c_act;
+  c.acts[i] = acts;
+}
+
+// ---------------------------------------------------------------- launchers
+
+hipError_t launch_lock_cursor(const LockBuffers& B, int64_t n, const LaneCursor& c,
+                              hipStream_t st) {
+  hipLaunchKernelGGL(k_lock_cursor, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                     st, B, n, c);
+  return hipGetLastError();
+}
+
+int64_t policy_lds_limit() {
+  return std::min<int64_t>(lds_dynamic_max((const void*)k_policy_forward), 160 * 1024 - 2048);
+}
+
+hipError_t launch_policy_forward(const PolNet& N, const PolIO& io, hipStream_t st) {
+  if (io.n <= 0) return hipSuccess;
+  const int64_t bytes = policy_lds_bytes(N.depth, N.width_pi, N.width_vf);
+  if (bytes > policy_lds_limit()) return hipErrorInvalidValue;
+  CPR_LDS_GUARD(k_policy_forward, bytes);
+  if (bytes > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute((const void*)k_policy_forward,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)policy_lds_limit());
+    if (e != hipSuccess) return e;
+  }
+  const int32_t w = N.width_pi > N.width_vf ? N.width_pi : N.width_vf;
+  const int64_t blocks = (io.n + kPolRows - 1) / kPolRows;
+  hipLaunchKernelGGL(k_policy_forward, dim3((unsigned)blocks), dim3(kPolThreads), (size_t)bytes, st, N,
+                     io, (int32_t)policy_act_stride(w));
+  return hipGetLastError();
+}
+
+hipError_t launch_policy_collect(const PolCollect& C, int64_t n, hipStream_t st) {
+  hipLaunchKernelGGL(k_policy_collect, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                     st, C, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_policy_tail(const int64_t* acts, const int64_t* acts0, int64_t n,
+                              cpr_summary* sum, hipStream_t st) {
+  hipLaunchKernelGGL(k_policy_tail, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                     st, acts, acts0, n, sum);
+  return hipGetLastError();
+}
+
+}  // namespace cpr

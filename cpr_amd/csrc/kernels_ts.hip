@@ -595,6 +595,12 @@ hipError_t launch_ts_observe_fields(const ts::TsParams& P, uint8_t* mem, int64_t
   return hipGetLastError();
 }
 
+hipError_t launch_ts_cursor(const void* slots, int64_t n, const LaneCursor& c, hipStream_t st) {
+  hipLaunchKernelGGL(k_slot_cursor<TsSlot>, dim3(ts_grid(n)), dim3(kBlock), 0, st,
+                     (const TsSlot*)slots, n, c);
+  return hipGetLastError();
+}
+
 hipError_t launch_ts_policy(int32_t policy, int32_t k, int unit, const double* obs, int64_t n,
                             const uint8_t* table, int32_t dim, int32_t* actions,
                             hipStream_t st) {

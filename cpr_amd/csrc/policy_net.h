@@ -1,0 +1,103 @@
+// Parameter structs and launchers of the neural-network policy kernels
+// (kernels_policy.hip): a batched actor-critic MLP evaluated next to the lockstep lanes
+// (cpr_policy_net_forward, cpr_rollout_net). DESIGN.md §4.14.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/cpr_hip.h"
+
+namespace cpr {
+
+constexpr int kPolMaxDepth = 4;     // hidden layers per trunk
+constexpr int kPolMaxWidth = 512;   // units of a hidden layer (a multiple of 16)
+constexpr int kPolMaxExtra = 8;     // constants appended to the observation
+constexpr int kPolMaxActions = 24;  // widest action head (Ethereum)
+constexpr int kPolRows = 64;        // rows (lanes) a workgroup owns
+constexpr int kPolKT = 32;          // K extent of one staged weight chunk
+constexpr int kPolNT = 64;          // output units of one staged weight chunk (16 per wave)
+constexpr int kPolInStride = 20;    // floats per row of the input tile (obs_len + n_extra <= 18)
+constexpr int kPolWsStride = kPolKT + 4;
+constexpr int kPolLogitStride = kPolMaxActions + 1;
+
+// one Linear layer: W [n_out][n_in] row-major (torch.nn.Linear), b [n_out]; device pointers
+struct PolLayer {
+  const float* W;
+  const float* b;
+  int32_t n_in, n_out;
+};
+
+// the network on the device: layers 0 .. depth-1 of a trunk are its hidden layers, layer
+// `depth` its head (n_actions / 1 outputs)
+struct PolNet {
+  int32_t obs_len, n_extra, depth, n_actions;
+  int32_t width_pi, width_vf;
+  float extra[kPolMaxExtra];
+  PolLayer pi[kPolMaxDepth + 1];
+  PolLayer vf[kPolMaxDepth + 1];
+};
+
+// one forward over n rows (device pointers; outputs optional)
+struct PolIO {
+  const double* obs;    // [n][obs_len]
+  int64_t n;
+  int32_t deterministic;
+  uint64_t seed;
+  const uint64_t* ep;   // [n] episode of each row's draw; null: episode0 + row
+  uint64_t episode0;
+  const int64_t* step;  // [n] episode step index of each row's draw; null: 0
+  int32_t* action;      // [n]
+  double* logp;         // [n]
+  double* value;        // [n]
+  float* logits;        // [n][n_actions]
+};
+
+// floats per row of a hidden-activation tile: the padding makes the 16 rows x 4 k of an
+// MFMA operand read fall on 64 distinct LDS banks (width is a multiple of 16)
+inline int64_t policy_act_stride(int32_t width) { return (int64_t)width + 4; }
+
+// dynamic LDS bytes of k_policy_forward (the budget formula of DESIGN.md §4.14): the input
+// tile, one hidden tile (two from depth 2 on: a layer reads one and writes the other) of the
+// wider trunk, the weight chunk, logits and values of the workgroup's rows
+inline int64_t policy_lds_bytes(int32_t depth, int32_t width_pi, int32_t width_vf) {
+  const int32_t w = width_pi > width_vf ? width_pi : width_vf;
+  const int64_t hidden = (int64_t)kPolRows * policy_act_stride(w) * (depth >= 2 ? 2 : 1);
+  const int64_t fixed = (int64_t)kPolRows * kPolInStride + (int64_t)kPolNT * kPolWsStride +
+                        (int64_t)kPolRows * kPolLogitStride + kPolRows;
+  return 4 * (hidden + fixed);
+}
+
+// the most dynamic LDS k_policy_forward may ask for on the current device
+int64_t policy_lds_limit();
+hipError_t launch_policy_forward(const PolNet& N, const PolIO& io, hipStream_t st);
+
+// per-step bookkeeping of cpr_rollout_net over n lanes (device pointers)
+struct PolCollect {
+  // the step's outputs (StepBuffers of the lockstep step kernels)
+  const double* reward;
+  const uint8_t* done;
+  const double* era;
+  const double* erd;
+  const double* eprog;
+  const int64_t* esteps;
+  const int64_t* eacts;
+  const int32_t* hh;
+  const uint32_t* status;
+  int32_t orphans_from_progress;  // B_k, Tailstorm: orphans = activations - progress
+  // step-major outputs at this step (optional)
+  double* out_reward;
+  uint8_t* out_done;
+  // lane cursors: episode id, episode step index, activations of the episode already counted
+  uint64_t* ep;
+  int64_t* step;
+  int64_t* acts0;
+  uint8_t* mask;  // reset mask of this step
+  cpr_summary* sum;
+};
+hipError_t launch_policy_collect(const PolCollect& C, int64_t n, hipStream_t st);
+// after the last step: activations of the episodes still running (acts[i] - acts0[i])
+hipError_t launch_policy_tail(const int64_t* acts, const int64_t* acts0, int64_t n,
+                              cpr_summary* sum, hipStream_t st);
+
+}  // namespace cpr

@@ -172,6 +172,125 @@ def make_config(
     return c, keep
 
 
+def _f32(name, a):
+    """A C-contiguous float32 numpy copy of a numpy array or torch tensor."""
+    if hasattr(a, "detach"):  # torch tensor (torch is not imported here)
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.dtype.kind not in "fiu":
+        raise TypeError(f"{name}: expected a numeric array, got dtype {a.dtype}")
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{name}: non-finite value")
+    return a
+
+
+class PolicyNet:
+    """An actor-critic MLP for ``Batch.set_policy_net``: SB3's MlpPolicy shape (separate pi
+    and vf trunks, ReLU, linear heads; experiments/train/ppo.py:400-416).
+
+    ``pi`` / ``vf``: lists of (W, b) per hidden layer, W [out, in] as torch.nn.Linear (numpy
+    arrays or torch tensors); ``pi_head`` = (W [n_actions, width_pi], b), ``vf_head`` =
+    (W [1, width_vf], b); ``extra``: constants appended to every observation (the alpha,
+    gamma features of AssumptionScheduleWrapper). Both trunks have the same depth (1..4);
+    every width is a multiple of 16 in [16, 512]."""
+
+    def __init__(self, pi, pi_head, vf, vf_head, extra=()):
+        self.extra = tuple(float(x) for x in extra)
+        if len(self.extra) > L.POLICY_NET_MAX_EXTRA:
+            raise ValueError(f"extra: at most {L.POLICY_NET_MAX_EXTRA} values")
+        if not all(math.isfinite(x) for x in self.extra):
+            raise ValueError("extra: non-finite value")
+        if len(pi) != len(vf):
+            raise ValueError(f"pi / vf: depths differ ({len(pi)} and {len(vf)} hidden layers)")
+        if not 1 <= len(pi) <= L.POLICY_NET_MAX_DEPTH:
+            raise ValueError(f"pi: depth {len(pi)}, expected 1..{L.POLICY_NET_MAX_DEPTH}")
+        self.depth = len(pi)
+        self.pi = self._trunk("pi", pi)
+        self.vf = self._trunk("vf", vf)
+        if self.pi[0][0].shape[1] != self.vf[0][0].shape[1]:
+            raise ValueError("vf[0]: input width differs from pi[0]")
+        self.n_in = self.pi[0][0].shape[1]
+        self.width_pi = self.pi[0][0].shape[0]
+        self.width_vf = self.vf[0][0].shape[0]
+        self.pi_head = self._layer("pi_head", pi_head, self.width_pi, None)
+        self.vf_head = self._layer("vf_head", vf_head, self.width_vf, 1)
+        self.n_actions = self.pi_head[0].shape[0]
+
+    @staticmethod
+    def _layer(name, wb, n_in, n_out):
+        w, b = wb
+        w, b = _f32(name + " weight", w), _f32(name + " bias", b)
+        if w.ndim != 2 or b.ndim != 1 or b.shape[0] != w.shape[0]:
+            raise ValueError(f"{name}: expected W [out, in] and b [out], got "
+                             f"{list(w.shape)} and {list(b.shape)}")
+        if n_in is not None and w.shape[1] != n_in:
+            raise ValueError(f"{name}: input width {w.shape[1]}, expected {n_in}")
+        if n_out is not None and w.shape[0] != n_out:
+            raise ValueError(f"{name}: {w.shape[0]} outputs, expected {n_out}")
+        return w, b
+
+    @classmethod
+    def _trunk(cls, name, layers):
+        out = []
+        for i, wb in enumerate(layers):
+            w, b = cls._layer(f"{name}[{i}]", wb, out[-1][0].shape[0] if out else None, None)
+            width = w.shape[0]
+            if width % 16 != 0 or not 16 <= width <= 512:
+                raise ValueError(f"{name}[{i}]: width {width} is not a multiple of 16 in "
+                                 f"[16, 512]")
+            if out and width != out[0][0].shape[0]:
+                raise ValueError(f"{name}[{i}]: width {width} differs from {name}[0]'s "
+                                 f"{out[0][0].shape[0]}")
+            out.append((w, b))
+        return out
+
+    @classmethod
+    def from_state_dict(cls, sd, extra=()):
+        """From an SB3 ActorCriticPolicy state dict (or any torch module with its names):
+        mlp_extractor.policy_net.{0,2,4,...}.{weight,bias}, mlp_extractor.value_net.*,
+        action_net.*, value_net.*. stable_baselines3 is not imported."""
+        def trunk(prefix):
+            idx = sorted({int(k[len(prefix):].split(".")[0]) for k in sd if k.startswith(prefix)})
+            if not idx:
+                raise KeyError(f"state dict has no {prefix}*")
+            return [(sd[f"{prefix}{i}.weight"], sd[f"{prefix}{i}.bias"]) for i in idx]
+
+        return cls(pi=trunk("mlp_extractor.policy_net."),
+                   pi_head=(sd["action_net.weight"], sd["action_net.bias"]),
+                   vf=trunk("mlp_extractor.value_net."),
+                   vf_head=(sd["value_net.weight"], sd["value_net.bias"]), extra=extra)
+
+    def cstruct(self):
+        """The cpr_policy_net over this object's arrays (which must outlive the call)."""
+        c = L.PolicyNetC()
+        c.n_extra = len(self.extra)
+        for i, x in enumerate(self.extra):
+            c.extra[i] = x
+        c.depth = self.depth
+        c.width_pi = self.width_pi
+        c.width_vf = self.width_vf
+        for i in range(self.depth):
+            c.pi_w[i], c.pi_b[i] = self.pi[i][0].ctypes.data, self.pi[i][1].ctypes.data
+            c.vf_w[i], c.vf_b[i] = self.vf[i][0].ctypes.data, self.vf[i][1].ctypes.data
+        c.pi_head_w, c.pi_head_b = self.pi_head[0].ctypes.data, self.pi_head[1].ctypes.data
+        c.vf_head_w, c.vf_head_b = self.vf_head[0].ctypes.data, self.vf_head[1].ctypes.data
+        return c
+
+    def forward_f64(self, obs):
+        """Reference forward in numpy float64 on the f32-rounded inputs: (logits, value)."""
+        x = np.asarray(obs, dtype=np.float64).astype(np.float32).astype(np.float64)
+        x = np.concatenate([x, np.tile(np.float32(self.extra).astype(np.float64),
+                                       (x.shape[0], 1))], axis=1)
+        outs = []
+        for trunk, head in ((self.pi, self.pi_head), (self.vf, self.vf_head)):
+            h = x
+            for w, b in trunk:
+                h = np.maximum(h @ w.astype(np.float64).T + b.astype(np.float64), 0.0)
+            outs.append(h @ head[0].astype(np.float64).T + head[1].astype(np.float64))
+        return outs[0], outs[1][:, 0]
+
+
 class Batch:
     def __init__(self, config, ctx=None, keep=None):
         self.ctx = ctx or default_context()
@@ -354,6 +473,84 @@ class Batch:
         L.check(L.lib().cpr_rollout(self.handle, int(n_steps), L.ptr(obs), L.ptr(rew),
                                     L.ptr(done), 0, ctypes.byref(s)))
         return s, obs, rew, done.astype(bool)
+
+    # ---- neural-network policies (cpr_policy_net_set / _forward, cpr_rollout_net)
+    def set_policy_net(self, net):
+        """Upload a ``PolicyNet`` (replacing any earlier one). Its input width must be
+        obs_len + len(extra) and its action head n_actions of this batch."""
+        if not isinstance(net, PolicyNet):
+            raise TypeError("net: expected a PolicyNet")
+        n_act = self.observation_spec()[1]
+        if net.n_in != self.obs_len + len(net.extra):
+            raise ValueError(f"pi[0]/vf[0]: input width {net.n_in}, this batch needs obs_len "
+                             f"{self.obs_len} + {len(net.extra)} extra")
+        if net.n_actions != n_act:
+            raise ValueError(f"pi_head: {net.n_actions} actions, this batch has {n_act}")
+        L.check(L.lib().cpr_policy_net_set(self.handle, ctypes.byref(net.cstruct())))
+        self._net = net
+
+    def policy_net_forward(self, obs, deterministic=True, episode0=0, logits=False):
+        """The network on observation rows [n, obs_len]: (actions int32, logp f64, value
+        f64[, logits f32 [n, n_actions]]). Sampled mode draws row r at (episode
+        episode0 + r, step 0)."""
+        o = np.ascontiguousarray(np.atleast_2d(obs), dtype=np.float64)
+        if o.ndim != 2 or o.shape[1] != self.obs_len:
+            raise ValueError(f"obs: expected [n, {self.obs_len}], got {list(o.shape)}")
+        n = o.shape[0]
+        if n < 1:
+            raise ValueError("obs: at least one row")
+        act = np.zeros(n, dtype=np.int32)
+        logp = np.zeros(n)
+        val = np.zeros(n)
+        lg = np.zeros((n, self.observation_spec()[1]), dtype=np.float32) if logits else None
+        L.check(L.lib().cpr_policy_net_forward(
+            self.handle, L.ptr(o), n, 1 if deterministic else 0, int(episode0), L.ptr(act),
+            L.ptr(logp), L.ptr(val), L.ptr(lg)))
+        return (act, logp, val, lg) if logits else (act, logp, val)
+
+    ROLLOUT_NET_OUTPUTS = ("obs0", "obs", "action", "reward", "done", "logp", "value")
+
+    def rollout_net(self, n_steps, deterministic=False, outputs=True, summary=None,
+                    device_outputs=None):
+        """Rollout driven by the batch's network (cpr_rollout_net): per step the network
+        forward, the lockstep step, bookkeeping and auto-reset run on the device with no host
+        synchronisation. Returns (summary, arrays): ``outputs=True`` gives host arrays
+        obs0 [n_lanes, obs_len], obs [n_steps, n_lanes, obs_len], action, reward, done, logp
+        [n_steps, n_lanes] and value [n_steps + 1, n_lanes] (row n_steps: the bootstrap value);
+        ``device_outputs={name: device pointer}`` (e.g. torch tensors' ``data_ptr()``) writes
+        those buffers on the device instead and returns the same dict."""
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps: at least 1")
+        s = summary if summary is not None else L.Summary()
+        n = self.n_lanes
+        o = L.RolloutNetOut()
+        if device_outputs is not None:
+            for k, v in device_outputs.items():
+                if k not in self.ROLLOUT_NET_OUTPUTS:
+                    raise ValueError(f"device_outputs: unknown output {k!r}")
+                setattr(o, k, None if v is None else int(v))
+            L.check(L.lib().cpr_rollout_net(self.handle, n_steps, 1 if deterministic else 0,
+                                            ctypes.byref(o), 1, ctypes.byref(s)))
+            return s, device_outputs
+        arrays = {}
+        if outputs:
+            arrays = {
+                "obs0": np.zeros((n, self.obs_len)),
+                "obs": np.zeros((n_steps, n, self.obs_len)),
+                "action": np.zeros((n_steps, n), dtype=np.int32),
+                "reward": np.zeros((n_steps, n)),
+                "done": np.zeros((n_steps, n), dtype=np.uint8),
+                "logp": np.zeros((n_steps, n)),
+                "value": np.zeros((n_steps + 1, n)),
+            }
+            for k, v in arrays.items():
+                setattr(o, k, v.ctypes.data)
+        L.check(L.lib().cpr_rollout_net(self.handle, n_steps, 1 if deterministic else 0,
+                                        ctypes.byref(o), 0, ctypes.byref(s)))
+        if outputs:
+            arrays["done"] = arrays["done"].astype(bool)
+        return s, arrays
 
     def observation_spec(self):
         ol = ctypes.c_int32()

@@ -461,6 +461,85 @@ int cpr_observe_fields(cpr_batch* b, int32_t* fields);
 int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint8_t* done,
                 int outputs_on_device, cpr_summary* summary);
 
+/* Neural-network policies on the device (added within v11; nothing above changes).
+ *
+ * An actor-critic MLP as SB3's MlpPolicy builds it (experiments/train/ppo.py:400-416):
+ * separate pi and vf trunks of `depth` hidden layers (1..CPR_POLICY_NET_MAX_DEPTH) with
+ * ReLU after each, width_pi / width_vf units (multiples of 16 in [16, 512]), a linear
+ * action head (n_actions of cpr_observation_spec) and a linear value head (1). The input
+ * row is the lane's observation converted to f32 followed by the n_extra constants
+ * extra[0..n_extra) (the alpha, gamma features of AssumptionScheduleWrapper, constant
+ * within a batch). Weights are f32, row-major [out][in] like torch.nn.Linear: layer l of a
+ * trunk is w[l] [width][l == 0 ? obs_len + n_extra : width], b[l] [width]; heads are
+ * [n_actions][width_pi] and [1][width_vf]. All host pointers, copied by the call.
+ * Arithmetic is f32 in, f32 accumulate on the matrix cores; argmax, sampling and the
+ * log-probability are computed in f64 from the f32 logits l:
+ *   deterministic: the lowest index of the maximum logit
+ *   sampled: m = max l, e_i = exp(l_i - m), S = sum e_i in index order, action = the
+ *     smallest a with u S < sum_{i <= a} e_i (the last action if rounding leaves none),
+ *     u = u53(w0, w1) of the keyed block ctr = (episode, i, 0x60000000), key = seed, i = the
+ *     episode step index before the step: a draw depends on (seed, episode, step) only
+ *   logp = l_a - m - log S */
+#define CPR_POLICY_NET_MAX_DEPTH 4
+#define CPR_POLICY_NET_MAX_EXTRA 8
+typedef struct cpr_policy_net {
+  int32_t n_extra;
+  float extra[CPR_POLICY_NET_MAX_EXTRA];
+  int32_t depth;
+  int32_t width_pi;
+  int32_t width_vf;
+  const float* pi_w[CPR_POLICY_NET_MAX_DEPTH];
+  const float* pi_b[CPR_POLICY_NET_MAX_DEPTH];
+  const float* pi_head_w;
+  const float* pi_head_b;
+  const float* vf_w[CPR_POLICY_NET_MAX_DEPTH];
+  const float* vf_b[CPR_POLICY_NET_MAX_DEPTH];
+  const float* vf_head_w;
+  const float* vf_head_b;
+} cpr_policy_net;
+
+/* Set (or replace) the batch's network: shapes are checked against the batch, weights must
+ * be finite. CPR_E_UNSUPPORTED: FC16, a batch without lanes (n_lanes = 0), or a
+ * configuration whose workgroup tile needs more LDS than the device has (the widest trunk
+ * decides; two hidden tiles from depth 2 on) -- refused here, never
+ * launched. */
+int cpr_policy_net_set(cpr_batch* b, const cpr_policy_net* net);
+/* The network on n >= 1 observation rows (host buffers, obs [n][obs_len]); every output is
+ * optional: actions [n], logp [n], value [n], logits [n][n_actions]. Sampled mode
+ * (deterministic == 0) draws row r at (episode episode0 + r, step 0). CPR_E_STATE without a
+ * network. Synchronous. */
+int cpr_policy_net_forward(cpr_batch* b, const double* obs, int64_t n, int deterministic,
+                           uint64_t episode0, int32_t* actions, double* logp, double* value,
+                           float* logits);
+
+/* outputs of a network rollout; every pointer optional, step-major */
+typedef struct cpr_rollout_net_out {
+  double* obs0;    /* [n_lanes][obs_len] the observation before the first step */
+  double* obs;     /* [n_steps][n_lanes][obs_len] after step t (after a done: the new
+                      episode's first); the policy input of step t is obs0 / obs[t-1] */
+  int32_t* action; /* [n_steps][n_lanes] */
+  double* reward;  /* [n_steps][n_lanes] engine.ml:223 */
+  uint8_t* done;   /* [n_steps][n_lanes] */
+  double* logp;    /* [n_steps][n_lanes] log-probability of the action taken */
+  double* value;   /* [n_steps + 1][n_lanes] value of the policy input of step t; row n_steps
+                      is the value of the final observation (PPO's bootstrap) */
+} cpr_rollout_net_out;
+
+/* Lockstep rollout driven by the batch's network: per step, on the context's stream, the
+ * network forward on the lanes' observations, the protocol's lockstep step kernels (for
+ * Nakamoto the exact pass too: lanes that leave the closed form continue on the exact
+ * engine as under the host-driven step), the bookkeeping kernel and the protocol's reset
+ * kernel with a device mask; no host synchronisation until the end. Semantics as the
+ * built-in rollout above: continues from the lanes' state (a first call without a reset
+ * starts lane i at episode i), auto-reset at episode id + n_lanes, summary accumulated the
+ * same way; out may be NULL; device pointers if outputs_on_device != 0. The host-driven
+ * step, reset and the built-in rollout may follow and precede it. Sampled draws of a lane
+ * depend on (seed, episode, step) only, so chunking a rollout into calls changes nothing.
+ * CPR_E_STATE without a network. Synchronous; the launch timer covers the whole call. */
+int cpr_rollout_net(cpr_batch* b, int64_t n_steps, int deterministic,
+                    const cpr_rollout_net_out* out, int outputs_on_device,
+                    cpr_summary* summary);
+
 /* policy evaluated on encoded observations (host): obs n x obs_len -> actions n */
 int cpr_policy_actions(cpr_batch* b, int32_t policy, const double* obs, int64_t n,
                        int32_t* actions);

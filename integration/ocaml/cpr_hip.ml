@@ -241,6 +241,25 @@ let rollout =
     @-> ptr summary @-> returning int)
 ;;
 
+(* neural-network policies (added within ABI v11): cpr_policy_net and cpr_rollout_net_out
+   are passed as untyped pointers to caller-built C structs (include/cpr_hip.h) *)
+let policy_net_set =
+  foreign "cpr_policy_net_set" (ptr batch @-> ptr void @-> returning int)
+;;
+
+let policy_net_forward =
+  foreign
+    "cpr_policy_net_forward"
+    (ptr batch @-> ptr double @-> int64_t @-> int @-> uint64_t @-> ptr int32_t @-> ptr double
+    @-> ptr double @-> ptr float @-> returning int)
+;;
+
+let rollout_net =
+  foreign
+    "cpr_rollout_net"
+    (ptr batch @-> int64_t @-> int @-> ptr void @-> int @-> ptr summary @-> returning int)
+;;
+
 let policy_actions =
   foreign
     "cpr_policy_actions"

@@ -256,6 +256,41 @@ class RolloutNetOut(ctypes.Structure):
     ]
 
 
+# lane env (cpr_lane_env_set): enum cpr_gym_reward, enum cpr_reward_shape
+GYM_REWARD_ENGINE = 0
+GYM_REWARD_SPARSE_RELATIVE = 1
+GYM_REWARD_SPARSE_PER_PROGRESS = 2
+GYM_REWARD_DENSE_PER_PROGRESS = 3
+SHAPE_NONE = 0
+SHAPE_PER_ALPHA = 1
+SHAPE_CUT = 2
+LANE_ENV_MAX_ALPHA = 4096
+TAG_ASSUME = 0x70000000  # keyed-stream tag of an episode's alpha draw (lane_env.h)
+
+
+class LaneEnvC(ctypes.Structure):
+    """cpr_lane_env (include/cpr_hip.h)."""
+
+    _fields_ = [
+        ("n_alpha", ctypes.c_int32),
+        ("alpha", ctypes.c_void_p),
+        ("alpha_column", ctypes.c_int32),
+        ("gym_reward", ctypes.c_int32),
+        ("reward_shape", ctypes.c_int32),
+        ("dense_target", ctypes.c_double),
+    ]
+
+
+class RolloutEnvOut(ctypes.Structure):
+    """cpr_rollout_env_out: optional output buffers."""
+
+    _fields_ = [
+        ("alpha0", ctypes.c_void_p),
+        ("alpha", ctypes.c_void_p),
+        ("engine_reward", ctypes.c_void_p),
+    ]
+
+
 class CTrace(ctypes.Structure):
     _fields_ = [
         ("n_episodes", ctypes.c_int64),
@@ -373,6 +408,9 @@ EXPORTS = [
     "cpr_policy_net_set",
     "cpr_policy_net_forward",
     "cpr_rollout_net",
+    "cpr_lane_env_set",
+    "cpr_lane_alpha",
+    "cpr_rollout_net_env",
     "cpr_policy_actions",
     "cpr_observation_spec",
     "cpr_policy_count",
@@ -421,6 +459,10 @@ def _declare(L):
                                          vp, vp, vp]
     L.cpr_rollout_net.argtypes = [vp, ctypes.c_int64, ctypes.c_int, P(RolloutNetOut), ctypes.c_int,
                                   P(Summary)]
+    L.cpr_lane_env_set.argtypes = [vp, P(LaneEnvC)]
+    L.cpr_lane_alpha.argtypes = [vp, vp]
+    L.cpr_rollout_net_env.argtypes = [vp, ctypes.c_int64, ctypes.c_int, P(RolloutNetOut),
+                                      P(RolloutEnvOut), ctypes.c_int, P(Summary)]
     L.cpr_policy_actions.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int64, vp]
     L.cpr_observation_spec.argtypes = [vp, P(ctypes.c_int32), P(ctypes.c_int32), vp, vp]
     L.cpr_policy_count.argtypes = [ctypes.c_int32]

@@ -15,6 +15,7 @@
 #include "../../include/cpr_hip.h"
 #include "eth_window.h"
 #include "kernels.h"
+#include "lane_env.h"
 #include "nak_hybrid.h"
 #include "policy_net.h"
 
@@ -186,6 +187,12 @@ struct cpr_batch {
   bool has_net = false;
   PolNet pn;
   DevBuf pn_w, pn_step, pn_acts0, pn_acts, pn_in, pn_out;
+  // lane env (cpr_lane_env_set): the alpha table as thresholds and values, and per lane the
+  // current episode's threshold and alpha and the dense wrapper's accumulator
+  bool has_env = false;
+  cpr_lane_env env = {};  // n_alpha >= 1 once set (cfg.alpha alone without a table)
+  bool env_table = false; // the caller gave a table: cpr_rollout is refused
+  DevBuf le_tab_t, le_tab_a, le_lane_t, le_lane_a, le_acc;
   bool reset_done = false;
   int32_t tab_n = 4096;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1768,6 +1775,11 @@ static LockBuffers lock_buffers(cpr_batch* b) {
   return B;
 }
 
+// per-lane miner-draw thresholds of a batch with a lane env (null: cfg.alpha's, in the params)
+static const uint64_t* lane_thresholds(const cpr_batch* b) {
+  return b->has_env ? (const uint64_t*)b->le_lane_t.p : nullptr;
+}
+
 // the lanes' step-output buffers (l_obs, l_rew, l_done and the step infos in l_info)
 static StepBuffers step_buffers(cpr_batch* b) {
   const int64_t n = b->cfg.n_lanes;
@@ -1796,25 +1808,26 @@ static int launch_lock_step(cpr_batch* b, const int32_t* act, const StepBuffers&
   const int64_t n = b->cfg.n_lanes;
   hipStream_t st = b->ctx->stream;
   const double* tabs = (const double*)b->tabs_dev.p;
+  const uint64_t* lt = lane_thresholds(b);
   if (b->is_eth)
     HIP_TRY(launch_eth_step(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
                             b->bk_slots.p, n, act, b->cfg.unit_observation, tabs, b->tab_n, sb,
-                            st));
+                            st, lt));
   else if (b->cfg.protocol == CPR_PROTO_BK)
     HIP_TRY(launch_bk_step(b->BP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
                            b->bk_slots.p, n, act, b->cfg.unit_observation, tabs, b->tab_n, sb,
-                           st));
+                           st, lt));
   else if (b->cfg.protocol == CPR_PROTO_TAILSTORM)
     HIP_TRY(launch_ts_step(b->TP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
                            b->bk_slots.p, n, act, b->cfg.unit_observation, tabs, b->tab_n, sb,
-                           st));
+                           st, lt));
   else
   {
     const LockBuffers LB = lock_buffers(b);
     HIP_TRY(launch_step(b->P, b->cfg.seed, LB, n, act, b->cfg.unit_observation, tabs,
-                        tabs + b->tab_n, b->tab_n, sb, st));
+                        tabs + b->tab_n, b->tab_n, sb, st, lt));
     HIP_TRY(launch_lock_exact(b->NEP, b->cfg.seed, LB, n, act, b->cfg.unit_observation, tabs,
-                              tabs + b->tab_n, b->tab_n, sb, st));
+                              tabs + b->tab_n, b->tab_n, sb, st, lt));
   }
   return CPR_OK;
 }
@@ -1822,27 +1835,45 @@ static int launch_lock_step(cpr_batch* b, const int32_t* act, const StepBuffers&
 // The device side of a reset, shared by cpr_reset and cpr_rollout_net: the protocol's reset
 // kernel with a device mask and device episode ids (either may be null), every lane's
 // current observation into obs (device).
+// With a lane env the assumption schedule runs first (the event engines simulate up to the
+// first interaction inside reset): the masked lanes take their new episode's alpha, and
+// out_alpha (optional, device) gets every lane's.
 static int launch_lock_reset(cpr_batch* b, const uint8_t* dmask, const uint64_t* deps,
-                             double* obs) {
+                             double* obs, double* out_alpha = nullptr) {
   const int64_t n = b->cfg.n_lanes;
   hipStream_t st = b->ctx->stream;
   const double* tabs = (const double*)b->tabs_dev.p;
+  const uint64_t* lt = lane_thresholds(b);
+  if (b->has_env) {
+    LaneAssign A;
+    A.mask = dmask;
+    A.eps = deps;
+    A.seed = b->cfg.seed;
+    A.n_alpha = b->env.n_alpha;
+    A.tab_t = (const uint64_t*)b->le_tab_t.p;
+    A.tab_a = (const double*)b->le_tab_a.p;
+    A.lane_t = (uint64_t*)b->le_lane_t.p;
+    A.lane_alpha = (double*)b->le_lane_a.p;
+    A.dense_acc = (double*)b->le_acc.p;
+    A.out_alpha = out_alpha;
+    HIP_TRY(launch_lane_assign(A, n, st));
+  }
   if (b->is_eth)
     HIP_TRY(launch_eth_reset(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
                              b->bk_slots.p, n, dmask, deps, b->cfg.unit_observation, tabs,
-                             b->tab_n, obs, st));
+                             b->tab_n, obs, st, lt));
   else if (b->cfg.protocol == CPR_PROTO_BK)
     HIP_TRY(launch_bk_reset(b->BP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
                             b->bk_slots.p, n, dmask, deps, b->cfg.unit_observation, tabs,
-                            b->tab_n, obs, st));
+                            b->tab_n, obs, st, lt));
   else if (b->cfg.protocol == CPR_PROTO_TAILSTORM)
     HIP_TRY(launch_ts_reset(b->TP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->bk_bytes,
                             b->bk_slots.p, n, dmask, deps, b->cfg.unit_observation, tabs,
-                            b->tab_n, obs, st));
+                            b->tab_n, obs, st, lt));
   else
     HIP_TRY(launch_reset(b->P, b->NEP, b->cfg.seed, lock_buffers(b), n, dmask, deps,
                          b->cfg.unit_observation, tabs, tabs + b->tab_n, b->tab_n,
-                         obs, st));
+                         obs, st, lt));
   return CPR_OK;
 }
 
@@ -1933,7 +1964,8 @@ int cpr_observe_fields(cpr_batch* b, int32_t* fields) {
     HIP_TRY(launch_ts_observe_fields(b->TP, (uint8_t*)b->bk_lmem.p, b->bk_bytes, b->bk_slots.p,
                                      n, (int32_t*)tmp.p, st));
   else
-    HIP_TRY(launch_observe_fields(b->NEP, lock_buffers(b), n, (int32_t*)tmp.p, st));
+    HIP_TRY(launch_observe_fields(b->NEP, lock_buffers(b), n, (int32_t*)tmp.p, st,
+                                  lane_thresholds(b)));
   HIP_TRY(hipMemcpyAsync(fields, tmp.p, (size_t)n * per, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   tmp.release();
@@ -2208,6 +2240,9 @@ static int nak_rollout_rounds(cpr_batch* b, int64_t n_steps, double* obs, double
 int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint8_t* done,
                 int outputs_on_device, cpr_summary* summary) {
   if (!b || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (b->env_table)
+    return fail(CPR_E_UNSUPPORTED, "cpr_rollout (built-in policies) runs every lane at cfg.alpha; "
+                                   "this batch has an alpha table (cpr_lane_env_set)");
   const bool is_nak = !b->is_ev && !b->is_eth;
   if (is_nak) {
     // the closed-form lane's rollout (k_nak_rollout): the gym's networks, policies the lane
@@ -2335,6 +2370,9 @@ int cpr_policy_net_set(cpr_batch* b, const cpr_policy_net* net) {
   for (int i = 0; i < net->n_extra; i++)
     if (!std::isfinite(net->extra[i]))
       return fail(CPR_E_INVALID_ARG, "policy net: non-finite extra feature");
+  if (b->has_env && b->env.alpha_column >= net->n_extra)
+    return fail(CPR_E_INVALID_ARG, "policy net: n_extra does not reach the lane env's "
+                                   "alpha_column (cpr_lane_env_set)");
   int32_t ol = 0, na = 0;
   int rc = cpr_observation_spec(b, &ol, &na, nullptr, nullptr);
   if (rc) return rc;
@@ -2462,9 +2500,88 @@ static int launch_lane_cursor(cpr_batch* b, const LaneCursor& c) {
   return CPR_OK;
 }
 
+// ---------------------------------------------------------------- lane env (cpr-v0 layers)
+
+int cpr_lane_env_set(cpr_batch* b, const cpr_lane_env* env) {
+  if (!b || !env) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (b->cfg.protocol == CPR_PROTO_FC16)
+    return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
+  if (b->cfg.n_lanes <= 0 || b->cfg.mode != CPR_MODE_GYM)
+    return fail(CPR_E_UNSUPPORTED, "a lane env needs lockstep lanes (CPR_MODE_GYM, "
+                                   "cfg.n_lanes > 0)");
+  if (b->reset_done)
+    return fail(CPR_E_STATE, "cpr_lane_env_set after the batch's first reset or rollout");
+  const bool table = env->n_alpha != 0 || env->alpha != nullptr;
+  if (table && (env->n_alpha < 1 || env->n_alpha > kLaneEnvMaxAlpha || !env->alpha))
+    return fail(CPR_E_INVALID_ARG, "lane env: n_alpha must be in 1..4096 with a table (or 0 and "
+                                   "NULL for cfg.alpha)");
+  if (env->gym_reward < CPR_GYM_REWARD_ENGINE || env->gym_reward > CPR_GYM_REWARD_DENSE_PER_PROGRESS)
+    return fail(CPR_E_INVALID_ARG, "lane env: unknown gym_reward");
+  if (env->reward_shape < CPR_SHAPE_NONE || env->reward_shape > CPR_SHAPE_CUT)
+    return fail(CPR_E_INVALID_ARG, "lane env: unknown reward_shape");
+  if (env->gym_reward == CPR_GYM_REWARD_DENSE_PER_PROGRESS && !(env->dense_target > 0.0))
+    return fail(CPR_E_INVALID_ARG, "lane env: dense_target <= 0");
+  if (env->alpha_column < -1)
+    return fail(CPR_E_INVALID_ARG, "lane env: alpha_column < -1");
+  if (b->has_net && env->alpha_column >= b->pn.n_extra)
+    return fail(CPR_E_INVALID_ARG, "lane env: alpha_column >= n_extra of the batch's network");
+  std::vector<double> tab_a(table ? env->alpha : &b->cfg.alpha,
+                            table ? env->alpha + env->n_alpha : &b->cfg.alpha + 1);
+  const bool divides = env->reward_shape != CPR_SHAPE_NONE;
+  for (double a : tab_a) {
+    if (std::isnan(a)) return fail(CPR_E_INVALID_ARG, "alpha cannot be NaN");
+    if (a < 0. || a > 1.) return fail(CPR_E_INVALID_ARG, "alpha < 0 || alpha > 1");
+    if (divides && !(a > 0.))
+      return fail(CPR_E_INVALID_ARG, "lane env: the reward shape divides by alpha, which is 0");
+  }
+  std::vector<uint64_t> tab_t(tab_a.size());
+  for (size_t i = 0; i < tab_a.size(); i++) tab_t[i] = alpha_threshold(tab_a[i]);
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  const size_t n = (size_t)b->cfg.n_lanes;
+  // before the first reset every lane stands at cfg.alpha
+  const std::vector<double> la(n, b->cfg.alpha), zero(n, 0.0);
+  const std::vector<uint64_t> lt(n, alpha_threshold(b->cfg.alpha));
+  HIP_TRY(b->le_tab_t.ensure(tab_t.size() * 8));
+  HIP_TRY(b->le_tab_a.ensure(tab_a.size() * 8));
+  HIP_TRY(b->le_lane_t.ensure(n * 8));
+  HIP_TRY(b->le_lane_a.ensure(n * 8));
+  HIP_TRY(b->le_acc.ensure(n * 8));
+  HIP_TRY(hipMemcpy(b->le_tab_t.p, tab_t.data(), tab_t.size() * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->le_tab_a.p, tab_a.data(), tab_a.size() * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->le_lane_t.p, lt.data(), n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->le_lane_a.p, la.data(), n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->le_acc.p, zero.data(), n * 8, hipMemcpyHostToDevice));
+  b->env = *env;
+  b->env.alpha = nullptr;
+  b->env.n_alpha = (int32_t)tab_a.size();
+  b->env_table = table;
+  b->has_env = true;
+  return CPR_OK;
+}
+
+int cpr_lane_alpha(cpr_batch* b, double* alpha) {
+  if (!b || !alpha) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  const int64_t n = b->cfg.n_lanes;
+  if (!b->has_env) {
+    for (int64_t i = 0; i < n; i++) alpha[i] = b->cfg.alpha;
+    return CPR_OK;
+  }
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  hipStream_t st = b->ctx->stream;
+  HIP_TRY(hipMemcpyAsync(alpha, b->le_lane_a.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CPR_OK;
+}
+
 int cpr_rollout_net(cpr_batch* b, int64_t n_steps, int deterministic,
                     const cpr_rollout_net_out* out, int outputs_on_device,
                     cpr_summary* summary) {
+  return cpr_rollout_net_env(b, n_steps, deterministic, out, nullptr, outputs_on_device, summary);
+}
+
+int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
+                        const cpr_rollout_net_out* out, const cpr_rollout_env_out* env_out,
+                        int outputs_on_device, cpr_summary* summary) {
   if (!b || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
   if (b->cfg.protocol == CPR_PROTO_FC16)
     return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
@@ -2490,19 +2607,25 @@ int cpr_rollout_net(cpr_batch* b, int64_t n_steps, int deterministic,
   cpr_rollout_net_out H = {};
   if (out) H = *out;
   cpr_rollout_net_out D = H;
+  cpr_rollout_env_out HE = {};
+  if (env_out) HE = *env_out;
+  cpr_rollout_env_out DE = HE;
   struct Stage {
     void** dev;
     void* host;
     size_t bytes;
     DevBuf buf;
   };
-  Stage stage[7] = {{(void**)&D.obs0, H.obs0, (size_t)n * ol * 8, {}},
+  Stage stage[10] = {{(void**)&D.obs0, H.obs0, (size_t)n * ol * 8, {}},
                     {(void**)&D.obs, H.obs, (size_t)cells * ol * 8, {}},
                     {(void**)&D.action, H.action, (size_t)cells * 4, {}},
                     {(void**)&D.reward, H.reward, (size_t)cells * 8, {}},
                     {(void**)&D.done, H.done, (size_t)cells, {}},
                     {(void**)&D.logp, H.logp, (size_t)cells * 8, {}},
-                    {(void**)&D.value, H.value, (size_t)(cells + n) * 8, {}}};
+                    {(void**)&D.value, H.value, (size_t)(cells + n) * 8, {}},
+                    {(void**)&DE.alpha0, HE.alpha0, (size_t)n * 8, {}},
+                    {(void**)&DE.alpha, HE.alpha, (size_t)cells * 8, {}},
+                    {(void**)&DE.engine_reward, HE.engine_reward, (size_t)cells * 8, {}}};
   if (!outputs_on_device)
     for (Stage& s : stage)
       if (s.host) {
@@ -2516,7 +2639,16 @@ int cpr_rollout_net(cpr_batch* b, int64_t n_steps, int deterministic,
   // and writes every lane's current observation into l_obs (cpr_rollout leaves none there)
   const bool fresh = !b->reset_done;
   if (!fresh) HIP_TRY(hipMemsetAsync(b->l_mask.p, 0, (size_t)n, st));
-  rc = launch_lock_reset(b, fresh ? nullptr : (const uint8_t*)b->l_mask.p, nullptr, sb.obs);
+  // without a lane env every episode runs at cfg.alpha: the alpha outputs are that constant
+  const bool env = b->has_env;
+  if (!env && (DE.alpha0 || DE.alpha)) {
+    const std::vector<double> ca((size_t)(DE.alpha ? cells : n), b->cfg.alpha);
+    if (DE.alpha0) HIP_TRY(hipMemcpyAsync(DE.alpha0, ca.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if (DE.alpha) HIP_TRY(hipMemcpyAsync(DE.alpha, ca.data(), (size_t)cells * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));  // ca leaves scope
+  }
+  rc = launch_lock_reset(b, fresh ? nullptr : (const uint8_t*)b->l_mask.p, nullptr, sb.obs,
+                         env ? DE.alpha0 : nullptr);
   if (rc) return rc;
   LaneCursor cur;
   cur.ep = (uint64_t*)b->l_eps.p;
@@ -2533,6 +2665,11 @@ int cpr_rollout_net(cpr_batch* b, int64_t n_steps, int deterministic,
   io.seed = b->cfg.seed;
   io.ep = cur.ep;
   io.step = cur.steps;
+  io.alpha_col = -1;
+  if (env && b->env.alpha_column >= 0) {
+    io.lane_alpha = (const double*)b->le_lane_a.p;
+    io.alpha_col = b->env.alpha_column;
+  }
   PolCollect C = {};
   C.reward = sb.reward;
   C.done = sb.done;
@@ -2549,6 +2686,13 @@ int cpr_rollout_net(cpr_batch* b, int64_t n_steps, int deterministic,
   C.acts0 = cur.acts;
   C.mask = (uint8_t*)b->l_mask.p;
   C.sum = (cpr_summary*)b->summary.p;
+  if (env) {
+    C.gym_reward = b->env.gym_reward;
+    C.reward_shape = b->env.reward_shape;
+    C.dense_target = b->env.dense_target;
+    C.lane_alpha = (const double*)b->le_lane_a.p;
+    C.dense_acc = (double*)b->le_acc.p;
+  }
   // the policy input of step t: l_obs before the first step, then where the reset kernel
   // of step t - 1 wrote every lane's observation (the caller's obs row, or l_obs)
   const double* in_obs = sb.obs;
@@ -2563,9 +2707,11 @@ int cpr_rollout_net(cpr_batch* b, int64_t n_steps, int deterministic,
     if (rc) return rc;
     C.out_reward = D.reward ? D.reward + t * n : nullptr;
     C.out_done = D.done ? D.done + t * n : nullptr;
+    C.out_engine_reward = DE.engine_reward ? DE.engine_reward + t * n : nullptr;
     HIP_TRY(launch_policy_collect(C, n, st));
     double* next_obs = D.obs ? D.obs + t * n * ol : sb.obs;
-    rc = launch_lock_reset(b, C.mask, cur.ep, next_obs);
+    rc = launch_lock_reset(b, C.mask, cur.ep, next_obs,
+                           env && DE.alpha ? DE.alpha + t * n : nullptr);
     if (rc) return rc;
     in_obs = next_obs;
   }

@@ -34,6 +34,10 @@
 
 namespace cpr {
 
+// lane_t of the lockstep launchers below (reset, step, exact pass, observe): null, or the
+// per-lane miner-draw thresholds of a batch with a lane env (cpr_lane_env_set), which replace
+// the params' t_att in a per-thread copy; the lane and slot layouts are untouched
+
 // per-step outputs of the lockstep kernel (device pointers)
 struct StepBuffers {
   double* obs;
@@ -106,17 +110,17 @@ hipError_t launch_replay_episodes(const NakParams& P, const TraceSource& src, in
 hipError_t launch_reset(const NakParams& P, const eth::EthParams& EP, uint64_t seed,
                         const LockBuffers& B, int64_t n, const uint8_t* mask, const uint64_t* eps,
                         int unit, const double* tab_nn, const double* tab_sg, int32_t tab_n,
-                        double* obs, hipStream_t st);
+                        double* obs, hipStream_t st, const uint64_t* lane_t = nullptr);
 hipError_t launch_step(const NakParams& P, uint64_t seed, const LockBuffers& B, int64_t n,
                        const int32_t* actions, int unit, const double* tab_nn,
                        const double* tab_sg, int32_t tab_n, const StepBuffers& b,
-                       hipStream_t st);
+                       hipStream_t st, const uint64_t* lane_t = nullptr);
 // after launch_step: lanes that left the closed form move to (or step on) the exact engine
 // (EP: the batch's Ethereum lane in Nakamoto mode) and their step outputs are rewritten
 hipError_t launch_lock_exact(const eth::EthParams& EP, uint64_t seed, const LockBuffers& B,
                              int64_t n, const int32_t* actions, int unit, const double* tab_nn,
                              const double* tab_sg, int32_t tab_n, const StepBuffers& b,
-                             hipStream_t st);
+                             hipStream_t st, const uint64_t* lane_t = nullptr);
 // what the passes of one cpr_rollout call over the Nakamoto lockstep lanes share (device
 // pointers; obs / reward / done optional, step-major)
 struct RollBuffers {
@@ -141,7 +145,7 @@ hipError_t launch_nak_rollout_exact(const NakParams& P, const eth::EthParams& EP
 // resident 256-lane workgroups per CU of the closed-form rollout kernel
 int nak_rollout_blocks_per_cu();
 hipError_t launch_observe_fields(const eth::EthParams& EP, const LockBuffers& B, int64_t n,
-                                 int32_t* f, hipStream_t st);
+                                 int32_t* f, hipStream_t st, const uint64_t* lane_t = nullptr);
 hipError_t launch_policy(int32_t policy, int unit, const double* obs, int64_t n,
                          const uint8_t* table, int32_t dim, int32_t* actions, hipStream_t st);
 hipError_t launch_stream_fill(uint64_t seed, uint64_t ep, uint32_t idx0, uint32_t tag, int64_t n,
@@ -224,11 +228,11 @@ int eth_win_blocks_per_cu(bool recs);
 hipError_t launch_eth_reset(const eth::EthParams& P, uint64_t seed, uint8_t* mem,
                             int64_t lane_bytes, void* slots, int64_t n, const uint8_t* mask,
                             const uint64_t* eps, int unit, const double* tabs, int32_t tn,
-                            double* obs, hipStream_t st);
+                            double* obs, hipStream_t st, const uint64_t* lane_t = nullptr);
 hipError_t launch_eth_step(const eth::EthParams& P, uint64_t seed, uint8_t* mem,
                            int64_t lane_bytes, void* slots, int64_t n, const int32_t* actions,
                            int unit, const double* tabs, int32_t tn, const StepBuffers& b,
-                           hipStream_t st);
+                           hipStream_t st, const uint64_t* lane_t = nullptr);
 hipError_t launch_eth_rollout(const eth::EthParams& P, uint64_t seed, uint8_t* mem,
                               int64_t lane_bytes, void* slots, int64_t n, int64_t n_steps,
                               int unit, const double* tabs, int32_t tn, double* obs,
@@ -312,10 +316,12 @@ hipError_t launch_bk_replay_episodes(const bk::BkParams& P, const TraceSource& s
                                    const NodeOut& no = NodeOut());
 hipError_t launch_bk_reset(const bk::BkParams& P, uint64_t seed, uint8_t* mem, int64_t lane_bytes,
                            void* slots, int64_t n, const uint8_t* mask, const uint64_t* eps,
-                           int unit, const double* tabs, int32_t tn, double* obs, hipStream_t st);
+                           int unit, const double* tabs, int32_t tn, double* obs, hipStream_t st,
+                           const uint64_t* lane_t = nullptr);
 hipError_t launch_bk_step(const bk::BkParams& P, uint64_t seed, uint8_t* mem, int64_t lane_bytes,
                           void* slots, int64_t n, const int32_t* actions, int unit,
-                          const double* tabs, int32_t tn, const StepBuffers& b, hipStream_t st);
+                          const double* tabs, int32_t tn, const StepBuffers& b, hipStream_t st,
+                          const uint64_t* lane_t = nullptr);
 hipError_t launch_bk_rollout(const bk::BkParams& P, uint64_t seed, uint8_t* mem,
                              int64_t lane_bytes, void* slots, int64_t n, int64_t n_steps,
                              int unit, const double* tabs, int32_t tn, double* obs,
@@ -338,10 +344,12 @@ hipError_t launch_ts_replay_episodes(const ts::TsParams& P, const TraceSource& s
                                    const NodeOut& no = NodeOut());
 hipError_t launch_ts_reset(const ts::TsParams& P, uint64_t seed, uint8_t* mem, int64_t lane_bytes,
                            void* slots, int64_t n, const uint8_t* mask, const uint64_t* eps,
-                           int unit, const double* tabs, int32_t tn, double* obs, hipStream_t st);
+                           int unit, const double* tabs, int32_t tn, double* obs, hipStream_t st,
+                           const uint64_t* lane_t = nullptr);
 hipError_t launch_ts_step(const ts::TsParams& P, uint64_t seed, uint8_t* mem, int64_t lane_bytes,
                           void* slots, int64_t n, const int32_t* actions, int unit,
-                          const double* tabs, int32_t tn, const StepBuffers& b, hipStream_t st);
+                          const double* tabs, int32_t tn, const StepBuffers& b, hipStream_t st,
+                          const uint64_t* lane_t = nullptr);
 hipError_t launch_ts_rollout(const ts::TsParams& P, uint64_t seed, uint8_t* mem,
                              int64_t lane_bytes, void* slots, int64_t n, int64_t n_steps,
                              int unit, const double* tabs, int32_t tn, double* obs,

@@ -242,13 +242,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ARR == 0
 
 // nak_to_eth_action, lock_mem, write_obs, lock_exact_mem: kernels_lock.h
 
+// LT: the launch has per-lane thresholds (lane_t). Two instantiations, because writing to
+// the by-value params makes a per-thread copy of them: the one without is the kernel as it
+// was
+template <bool LT>
 __global__ __launch_bounds__(kBlock) void k_reset(NakParams P, eth::EthParams EP, uint64_t seed,
                                                    LockBuffers B, int64_t n, const uint8_t* mask,
                                                    const uint64_t* eps, int unit,
                                                    const double* tab_nn, const double* tab_sg,
-                                                   int32_t tab_n, double* obs) {
+                                                   int32_t tab_n, double* obs,
+                                                   const uint64_t* lane_t) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if constexpr (LT) {  // the lane's own alpha (cpr_lane_env_set)
+    P.t_att = lane_t[i];
+    EP.t_att = lane_t[i];
+  }
   LockLane& LL = ((LockLane*)B.lanes)[i];
   if (mask != nullptr && !mask[i] && LL.exact > 0) {
     // a lane left unreset that runs on the exact engine: its observation is the exact
@@ -279,12 +288,15 @@ __global__ __launch_bounds__(kBlock) void k_reset(NakParams P, eth::EthParams EP
   write_obs(LL.L, unit, tab_nn, tab_sg, tab_n, obs + 4 * i);
 }
 
+template <bool LT>
 __global__ __launch_bounds__(kBlock) void k_step(NakParams P, uint64_t seed, LockBuffers B,
                                                   int64_t n, const int32_t* actions, int unit,
                                                   const double* tab_nn, const double* tab_sg,
-                                                  int32_t tab_n, StepBuffers out) {
+                                                  int32_t tab_n, StepBuffers out,
+                                                  const uint64_t* lane_t) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if constexpr (LT) P.t_att = lane_t[i];  // the lane's own alpha (cpr_lane_env_set)
   LockLane& LL = ((LockLane*)B.lanes)[i];
   if (B.alog && LL.steps < B.alog_cap) B.alog[i * B.alog_cap + LL.steps] = (uint8_t)actions[i];
   if (LL.exact) return;  // stepped on the exact engine by k_lock_exact
@@ -324,14 +336,18 @@ __global__ __launch_bounds__(kBlock) void k_step(NakParams P, uint64_t seed, Loc
 // draw with the actions it was given, and stays there until its next reset; this step's
 // outputs are rewritten from that lane (status: the closed form's bits | EXACT_RERUN)
 
+template <bool LT>
 __global__ __launch_bounds__(kBlock) void k_lock_exact(eth::EthParams EP, uint64_t seed,
                                                         LockBuffers B, int64_t n,
                                                         const int32_t* actions, int unit,
                                                         const double* tab_nn,
                                                         const double* tab_sg, int32_t tab_n,
-                                                        StepBuffers out) {
+                                                        StepBuffers out,
+                                                        const uint64_t* lane_t) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  // the replay from the lane's first draw and every later step use the lane's own alpha
+  if constexpr (LT) EP.t_att = lane_t[i];
   LockLane& LL = ((LockLane*)B.lanes)[i];
   eth::EthLane* slots = (eth::EthLane*)B.eslots;
   const Stream S = make_stream(seed, LL.ep);
@@ -387,9 +403,12 @@ __global__ __launch_bounds__(kBlock) void k_lock_exact(eth::EthParams EP, uint64
                    tab_sg, tab_n, out.obs + 4 * i);
 }
 
-__global__ void k_observe_fields(eth::EthParams EP, LockBuffers B, int64_t n, int32_t* f) {
+template <bool LT>
+__global__ void k_observe_fields(eth::EthParams EP, LockBuffers B, int64_t n, int32_t* f,
+                                 const uint64_t* lane_t) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if constexpr (LT) EP.t_att = lane_t[i];
   const LockLane& LL = ((const LockLane*)B.lanes)[i];
   if (LL.exact) {
     eth::EthLane E = ((eth::EthLane*)B.eslots)[LL.exact - 1];
@@ -571,38 +590,55 @@ hipError_t launch_replay_episodes(const NakParams& P, const TraceSource& src, in
 hipError_t launch_reset(const NakParams& P, const eth::EthParams& EP, uint64_t seed,
                         const LockBuffers& B, int64_t n, const uint8_t* mask, const uint64_t* eps,
                         int unit, const double* tab_nn, const double* tab_sg, int32_t tab_n,
-                        double* obs, hipStream_t st) {
+                        double* obs, hipStream_t st, const uint64_t* lane_t) {
   const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(kBlock), 0, st, P, EP, seed, B, n, mask, eps,
-                     unit, tab_nn, tab_sg, tab_n, obs);
+  if (lane_t)
+    hipLaunchKernelGGL(k_reset<true>, dim3(blocks), dim3(kBlock), 0, st, P, EP, seed, B, n, mask,
+                       eps, unit, tab_nn, tab_sg, tab_n, obs, lane_t);
+  else
+    hipLaunchKernelGGL(k_reset<false>, dim3(blocks), dim3(kBlock), 0, st, P, EP, seed, B, n, mask,
+                       eps, unit, tab_nn, tab_sg, tab_n, obs, lane_t);
   return hipGetLastError();
 }
 
 hipError_t launch_step(const NakParams& P, uint64_t seed, const LockBuffers& B, int64_t n,
                        const int32_t* actions, int unit, const double* tab_nn,
                        const double* tab_sg, int32_t tab_n, const StepBuffers& b,
-                       hipStream_t st) {
+                       hipStream_t st, const uint64_t* lane_t) {
   const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_step, dim3(blocks), dim3(kBlock), 0, st, P, seed, B, n, actions, unit,
-                     tab_nn, tab_sg, tab_n, b);
+  if (lane_t)
+    hipLaunchKernelGGL(k_step<true>, dim3(blocks), dim3(kBlock), 0, st, P, seed, B, n, actions,
+                       unit, tab_nn, tab_sg, tab_n, b, lane_t);
+  else
+    hipLaunchKernelGGL(k_step<false>, dim3(blocks), dim3(kBlock), 0, st, P, seed, B, n, actions,
+                       unit, tab_nn, tab_sg, tab_n, b, lane_t);
   return hipGetLastError();
 }
 
 hipError_t launch_lock_exact(const eth::EthParams& EP, uint64_t seed, const LockBuffers& B,
                              int64_t n, const int32_t* actions, int unit, const double* tab_nn,
                              const double* tab_sg, int32_t tab_n, const StepBuffers& b,
-                             hipStream_t st) {
+                             hipStream_t st, const uint64_t* lane_t) {
   if (!B.alog) return hipSuccess;
   const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_lock_exact, dim3(blocks), dim3(kBlock), 0, st, EP, seed, B, n, actions,
-                     unit, tab_nn, tab_sg, tab_n, b);
+  if (lane_t)
+    hipLaunchKernelGGL(k_lock_exact<true>, dim3(blocks), dim3(kBlock), 0, st, EP, seed, B, n,
+                       actions, unit, tab_nn, tab_sg, tab_n, b, lane_t);
+  else
+    hipLaunchKernelGGL(k_lock_exact<false>, dim3(blocks), dim3(kBlock), 0, st, EP, seed, B, n,
+                       actions, unit, tab_nn, tab_sg, tab_n, b, lane_t);
   return hipGetLastError();
 }
 
 hipError_t launch_observe_fields(const eth::EthParams& EP, const LockBuffers& B, int64_t n,
-                                 int32_t* f, hipStream_t st) {
+                                 int32_t* f, hipStream_t st, const uint64_t* lane_t) {
   const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_observe_fields, dim3(blocks), dim3(kBlock), 0, st, EP, B, n, f);
+  if (lane_t)
+    hipLaunchKernelGGL(k_observe_fields<true>, dim3(blocks), dim3(kBlock), 0, st, EP, B, n, f,
+                       lane_t);
+  else
+    hipLaunchKernelGGL(k_observe_fields<false>, dim3(blocks), dim3(kBlock), 0, st, EP, B, n, f,
+                       lane_t);
   return hipGetLastError();
 }
 

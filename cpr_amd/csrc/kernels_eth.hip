@@ -612,14 +612,18 @@ __device__ inline eth::EthMem eth_lane_mem(const eth::EthParams& P, uint8_t* mem
   return eth::eth_mem_at(mem + i * lane_bytes, P.cap_b, P.cap_e, P.n);
 }
 
+// LT: per-lane thresholds (lane_t); two instantiations, see k_reset in kernels.hip
+template <bool LT>
 __global__ __launch_bounds__(kBlock) void k_eth_reset(eth::EthParams P, uint64_t seed,
                                                        uint8_t* mem, int64_t lane_bytes,
                                                        EthSlot* slots, int64_t n,
                                                        const uint8_t* mask, const uint64_t* eps,
                                                        int unit, const double* tabs, int32_t tn,
-                                                       double* obs) {
+                                                       double* obs,
+                                                       const uint64_t* lane_t) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if constexpr (LT) P.t_att = lane_t[i];  // the lane's own alpha (cpr_lane_env_set)
   const eth::EthMem M = eth_lane_mem(P, mem, lane_bytes, i);
   EthSlot SL = slots[i];
   if (mask == nullptr || mask[i]) eth_slot_reset(P, seed, M, SL, eps ? eps[i] : (uint64_t)i);
@@ -641,14 +645,18 @@ __device__ inline void eth_info(const eth::EthParams& P, const eth::EthMem& M, E
   out.hm[i] = h.miner;
 }
 
+// LT: per-lane thresholds (lane_t); two instantiations, see k_reset in kernels.hip
+template <bool LT>
 __global__ __launch_bounds__(kBlock) void k_eth_step(eth::EthParams P, uint64_t seed,
                                                       uint8_t* mem, int64_t lane_bytes,
                                                       EthSlot* slots, int64_t n,
                                                       const int32_t* actions, int unit,
                                                       const double* tabs, int32_t tn,
-                                                      StepBuffers out) {
+                                                      StepBuffers out,
+                                                      const uint64_t* lane_t) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if constexpr (LT) P.t_att = lane_t[i];  // the lane's own alpha (cpr_lane_env_set)
   const eth::EthMem M = eth_lane_mem(P, mem, lane_bytes, i);
   EthSlot SL = slots[i];
   bool done = false;
@@ -774,20 +782,28 @@ static unsigned eth_grid_of(int64_t n) { return (unsigned)((n + kBlock - 1) / kB
 hipError_t launch_eth_reset(const eth::EthParams& P, uint64_t seed, uint8_t* mem,
                             int64_t lane_bytes, void* slots, int64_t n, const uint8_t* mask,
                             const uint64_t* eps, int unit, const double* tabs, int32_t tn,
-                            double* obs, hipStream_t st) {
+                            double* obs, hipStream_t st, const uint64_t* lane_t) {
   CPR_LAYOUT_GUARD(lane_bytes, eth::eth_lane_bytes(P.cap_b, P.cap_e, P.n));
-  hipLaunchKernelGGL(k_eth_reset, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
-                     lane_bytes, (EthSlot*)slots, n, mask, eps, unit, tabs, tn, obs);
+  if (lane_t)
+    hipLaunchKernelGGL(k_eth_reset<true>, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
+                       lane_bytes, (EthSlot*)slots, n, mask, eps, unit, tabs, tn, obs, lane_t);
+  else
+    hipLaunchKernelGGL(k_eth_reset<false>, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
+                       lane_bytes, (EthSlot*)slots, n, mask, eps, unit, tabs, tn, obs, lane_t);
   return hipGetLastError();
 }
 
 hipError_t launch_eth_step(const eth::EthParams& P, uint64_t seed, uint8_t* mem,
                            int64_t lane_bytes, void* slots, int64_t n, const int32_t* actions,
                            int unit, const double* tabs, int32_t tn, const StepBuffers& b,
-                           hipStream_t st) {
+                           hipStream_t st, const uint64_t* lane_t) {
   CPR_LAYOUT_GUARD(lane_bytes, eth::eth_lane_bytes(P.cap_b, P.cap_e, P.n));
-  hipLaunchKernelGGL(k_eth_step, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
-                     lane_bytes, (EthSlot*)slots, n, actions, unit, tabs, tn, b);
+  if (lane_t)
+    hipLaunchKernelGGL(k_eth_step<true>, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
+                       lane_bytes, (EthSlot*)slots, n, actions, unit, tabs, tn, b, lane_t);
+  else
+    hipLaunchKernelGGL(k_eth_step<false>, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
+                       lane_bytes, (EthSlot*)slots, n, actions, unit, tabs, tn, b, lane_t);
   return hipGetLastError();
 }
 

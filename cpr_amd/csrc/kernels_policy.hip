@@ -2,8 +2,11 @@
 //   k_policy_forward   the whole actor-critic MLP for a tile of rows per workgroup, on the
 //                      f32-input MFMA (v_mfma_f32_16x16x4_f32: f32 in, f32 accumulate), then
 //                      argmax / keyed sampling, log-probability and value per row in f64
-//   k_policy_collect   per-step bookkeeping of cpr_rollout_net: step-major outputs, summary
+//   k_policy_collect   per-step bookkeeping of cpr_rollout_net: step-major outputs (with a
+//                      lane env the gym's wrapped and shaped reward, lane_env.h), summary
 //                      of finished episodes, lane cursors, reset mask
+//   k_lane_assign      the lane env's assumption schedule: threshold and alpha of the masked
+//                      lanes' new episodes, before every lockstep reset
 //   k_policy_tail      activations of the episodes still running when the rollout ends
 //   k_lock_cursor      where the Nakamoto lockstep lanes stand when a rollout begins
 #include <hip/hip_runtime.h>
@@ -11,6 +14,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "lane_env.h"
 #include "nak_rollout.h"
 #include "policy_net.h"
 #include "summary.h"
@@ -129,7 +133,8 @@ __global__ __launch_bounds__(kPolThreads) void k_policy_forward(PolNet N, PolIO 
       if (c < N.obs_len)
         v = (float)io.obs[row * N.obs_len + c];
       else if (c < n_in)
-        v = N.extra[c - N.obs_len];
+        v = (io.lane_alpha && c - N.obs_len == io.alpha_col) ? (float)io.lane_alpha[row]
+                                                             : N.extra[c - N.obs_len];
     }
     xin[idx] = v;
   }
@@ -197,7 +202,22 @@ __global__ __launch_bounds__(kBlock) void k_policy_collect(PolCollect C, int64_t
   int64_t steps_all = 0, acts_all = 0;
   if (i < n) {
     const uint8_t d = C.done[i];
-    if (C.out_reward) C.out_reward[i] = C.reward[i];
+    double r = C.reward[i];
+    if (C.out_engine_reward) C.out_engine_reward[i] = r;
+    if (C.lane_alpha) {  // the gym's reward wrapper and shape (lane_env.h)
+      GymStepInfo s;
+      s.reward = r;
+      s.done = d != 0;
+      s.era = C.era[i];
+      s.erd = C.erd[i];
+      s.progress = C.eprog[i];
+      s.n_activations = C.eacts[i];
+      double acc = C.dense_acc[i];
+      r = gym_reward(C.gym_reward, C.dense_target, s, &acc);
+      if (C.gym_reward == CPR_GYM_REWARD_DENSE_PER_PROGRESS) C.dense_acc[i] = acc;
+      r = shape_reward(C.reward_shape, r, C.lane_alpha[i], s);
+    }
+    if (C.out_reward) C.out_reward[i] = r;
     if (C.out_done) C.out_done[i] = d;
     C.mask[i] = d;
     steps_all = 1;
@@ -232,6 +252,19 @@ __global__ __launch_bounds__(kBlock) void k_policy_tail(const int64_t* acts, con
   const int64_t v = wave_sum(i < n ? acts[i] - acts0[i] : 0);
   if ((threadIdx.x & 63) == 0 && v)
     atomicAdd((unsigned long long*)&sum->activations, (unsigned long long)v);
+}
+
+__global__ __launch_bounds__(kBlock) void k_lane_assign(LaneAssign A, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (A.mask == nullptr || A.mask[i]) {
+    const uint64_t ep = A.eps ? A.eps[i] : (uint64_t)i;
+    const int32_t j = lane_alpha_index(A.seed, ep, A.n_alpha);
+    A.lane_t[i] = A.tab_t[j];
+    A.lane_alpha[i] = A.tab_a[j];
+    A.dense_acc[i] = 0.0;
+  }
+  if (A.out_alpha) A.out_alpha[i] = A.lane_alpha[i];
 }
 
 // LaneCursor of the Nakamoto lockstep lanes (closed form, or the lane's exact-engine slot)
@@ -281,6 +314,12 @@ hipError_t launch_policy_forward(const PolNet& N, const PolIO& io, hipStream_t s
 hipError_t launch_policy_collect(const PolCollect& C, int64_t n, hipStream_t st) {
   hipLaunchKernelGGL(k_policy_collect, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                      st, C, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_lane_assign(const LaneAssign& A, int64_t n, hipStream_t st) {
+  hipLaunchKernelGGL(k_lane_assign, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                     st, A, n);
   return hipGetLastError();
 }
 

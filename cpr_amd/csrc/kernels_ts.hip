@@ -272,14 +272,18 @@ __device__ inline void ts_slot_reset(const ts::TsParams& P, uint64_t seed, const
   SL.L.gym_reset(P, make_stream(seed, ep), M);
 }
 
+// LT: per-lane thresholds (lane_t); two instantiations, see k_reset in kernels.hip
+template <bool LT>
 __global__ __launch_bounds__(kBlock) void k_ts_reset(ts::TsParams P, uint64_t seed, uint8_t* mem,
                                                       int64_t lane_bytes, TsSlot* slots,
                                                       int64_t n, const uint8_t* mask,
                                                       const uint64_t* eps, int unit,
                                                       const double* tabs, int32_t tn,
-                                                      double* obs) {
+                                                      double* obs,
+                                                      const uint64_t* lane_t) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if constexpr (LT) P.t_att = lane_t[i];  // the lane's own alpha (cpr_lane_env_set)
   const ts::TsMem M = ts::ts_mem_at(mem + i * lane_bytes, P);
   TsSlot SL = slots[i];
   if (mask == nullptr || mask[i]) ts_slot_reset(P, seed, M, SL, eps ? eps[i] : (uint64_t)i);
@@ -287,13 +291,17 @@ __global__ __launch_bounds__(kBlock) void k_ts_reset(ts::TsParams P, uint64_t se
   slots[i] = SL;
 }
 
+// LT: per-lane thresholds (lane_t); two instantiations, see k_reset in kernels.hip
+template <bool LT>
 __global__ __launch_bounds__(kBlock) void k_ts_step(ts::TsParams P, uint64_t seed, uint8_t* mem,
                                                      int64_t lane_bytes, TsSlot* slots,
                                                      int64_t n, const int32_t* actions, int unit,
                                                      const double* tabs, int32_t tn,
-                                                     StepBuffers out) {
+                                                     StepBuffers out,
+                                                     const uint64_t* lane_t) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if constexpr (LT) P.t_att = lane_t[i];  // the lane's own alpha (cpr_lane_env_set)
   const ts::TsMem M = ts::ts_mem_at(mem + i * lane_bytes, P);
   TsSlot SL = slots[i];
   const Stream S = make_stream(seed, SL.ep);
@@ -555,19 +563,28 @@ hipError_t launch_ts_replay_episodes(const ts::TsParams& P, const TraceSource& s
 hipError_t launch_ts_reset(const ts::TsParams& P, uint64_t seed, uint8_t* mem, int64_t lane_bytes,
                            void* slots, int64_t n, const uint8_t* mask, const uint64_t* eps,
                            int unit, const double* tabs, int32_t tn, double* obs,
-                           hipStream_t st) {
+                           hipStream_t st, const uint64_t* lane_t) {
   CPR_LAYOUT_GUARD(lane_bytes, ts::ts_lane_bytes(P));
-  hipLaunchKernelGGL(k_ts_reset, dim3(ts_grid(n)), dim3(kBlock), 0, st, P, seed, mem, lane_bytes,
-                     (TsSlot*)slots, n, mask, eps, unit, tabs, tn, obs);
+  if (lane_t)
+    hipLaunchKernelGGL(k_ts_reset<true>, dim3(ts_grid(n)), dim3(kBlock), 0, st, P, seed, mem,
+                       lane_bytes, (TsSlot*)slots, n, mask, eps, unit, tabs, tn, obs, lane_t);
+  else
+    hipLaunchKernelGGL(k_ts_reset<false>, dim3(ts_grid(n)), dim3(kBlock), 0, st, P, seed, mem,
+                       lane_bytes, (TsSlot*)slots, n, mask, eps, unit, tabs, tn, obs, lane_t);
   return hipGetLastError();
 }
 
 hipError_t launch_ts_step(const ts::TsParams& P, uint64_t seed, uint8_t* mem, int64_t lane_bytes,
                           void* slots, int64_t n, const int32_t* actions, int unit,
-                          const double* tabs, int32_t tn, const StepBuffers& b, hipStream_t st) {
+                          const double* tabs, int32_t tn, const StepBuffers& b, hipStream_t st,
+                          const uint64_t* lane_t) {
   CPR_LAYOUT_GUARD(lane_bytes, ts::ts_lane_bytes(P));
-  hipLaunchKernelGGL(k_ts_step, dim3(ts_grid(n)), dim3(kBlock), 0, st, P, seed, mem, lane_bytes,
-                     (TsSlot*)slots, n, actions, unit, tabs, tn, b);
+  if (lane_t)
+    hipLaunchKernelGGL(k_ts_step<true>, dim3(ts_grid(n)), dim3(kBlock), 0, st, P, seed, mem,
+                       lane_bytes, (TsSlot*)slots, n, actions, unit, tabs, tn, b, lane_t);
+  else
+    hipLaunchKernelGGL(k_ts_step<false>, dim3(ts_grid(n)), dim3(kBlock), 0, st, P, seed, mem,
+                       lane_bytes, (TsSlot*)slots, n, actions, unit, tabs, tn, b, lane_t);
   return hipGetLastError();
 }
 

@@ -51,6 +51,10 @@ struct PolIO {
   double* logp;         // [n]
   double* value;        // [n]
   float* logits;        // [n][n_actions]
+  // lane env (cpr_lane_env_set): extra column alpha_col of row r is (float)lane_alpha[r]
+  // instead of the constant; null / -1: constants only
+  const double* lane_alpha;  // [n]
+  int32_t alpha_col;
 };
 
 // floats per row of a hidden-activation tile: the padding makes the 16 rows x 4 k of an
@@ -94,8 +98,32 @@ struct PolCollect {
   int64_t* acts0;
   uint8_t* mask;  // reset mask of this step
   cpr_summary* sum;
+  // lane env (lane_env.h): reward wrapper and shape of out_reward, the lanes' alphas and
+  // dense accumulators (null: the engine's reward), the unwrapped reward (optional)
+  int32_t gym_reward, reward_shape;
+  double dense_target;
+  const double* lane_alpha;
+  double* dense_acc;
+  double* out_engine_reward;
 };
 hipError_t launch_policy_collect(const PolCollect& C, int64_t n, hipStream_t st);
+// The assumption schedule (lane_env.h): lanes with mask[i] != 0 (null: all) take the
+// threshold and alpha of their new episode eps[i] (null: the lane index) from the batch's
+// table and zero their dense accumulator; out_alpha (optional) gets every lane's alpha.
+// Runs before every lockstep reset launch of a batch with a lane env.
+struct LaneAssign {
+  const uint8_t* mask;
+  const uint64_t* eps;
+  uint64_t seed;
+  int32_t n_alpha;
+  const uint64_t* tab_t;  // [n_alpha] alpha_threshold of each entry
+  const double* tab_a;    // [n_alpha]
+  uint64_t* lane_t;       // [n]
+  double* lane_alpha;     // [n]
+  double* dense_acc;      // [n]
+  double* out_alpha;      // [n]
+};
+hipError_t launch_lane_assign(const LaneAssign& A, int64_t n, hipStream_t st);
 // after the last step: activations of the episodes still running (acts[i] - acts0[i])
 hipError_t launch_policy_tail(const int64_t* acts, const int64_t* acts0, int64_t n,
                               cpr_summary* sum, hipStream_t st);

@@ -302,6 +302,7 @@ class Batch:
         self.n_lanes = int(config.n_lanes)
         self.obs_len = self.observation_spec()[0]
         self._coverage_warned = False
+        self._lane_env = False
 
     def close(self):
         if self.handle:
@@ -508,7 +509,60 @@ class Batch:
             L.ptr(logp), L.ptr(val), L.ptr(lg)))
         return (act, logp, val, lg) if logits else (act, logp, val)
 
+    # ---- the gym layers of cpr-v0 over the lanes (cpr_lane_env_set)
+    GYM_REWARDS = {"engine": L.GYM_REWARD_ENGINE, "sparse_relative": L.GYM_REWARD_SPARSE_RELATIVE,
+                   "sparse_per_progress": L.GYM_REWARD_SPARSE_PER_PROGRESS,
+                   "dense_per_progress": L.GYM_REWARD_DENSE_PER_PROGRESS}
+    REWARD_SHAPES = {"none": L.SHAPE_NONE, "per_alpha": L.SHAPE_PER_ALPHA, "cut": L.SHAPE_CUT}
+
+    def set_lane_env(self, alphas=None, alpha_column=None, reward="engine", shape="none",
+                     dense_target=None):
+        """The assumption schedule and reward wrappers of cpr-v0 on the lanes, before the
+        first reset or rollout. ``alphas``: the table an episode's alpha is chosen from by
+        (seed, episode) (None: the config's alpha); ``alpha_column``: the column of the
+        network's extras that a rollout feeds with the lane's alpha (None: constants only);
+        ``reward`` in GYM_REWARDS, ``shape`` in REWARD_SHAPES ("per_alpha" is r / alpha, "cut"
+        is ppo.py's); ``dense_target``: episode_len of "dense_per_progress". They apply to
+        ``rollout_net``'s reward; ``step`` keeps the engine's."""
+        if reward not in self.GYM_REWARDS:
+            raise ValueError(f"reward: expected one of {sorted(self.GYM_REWARDS)}")
+        if shape not in self.REWARD_SHAPES:
+            raise ValueError(f"shape: expected one of {sorted(self.REWARD_SHAPES)}")
+        e = L.LaneEnvC()
+        tab = None
+        if alphas is not None:
+            tab = np.ascontiguousarray(np.atleast_1d(alphas), dtype=np.float64)
+            if tab.ndim != 1:
+                raise ValueError("alphas: expected a sequence of floats")
+            e.n_alpha = tab.size
+            e.alpha = tab.ctypes.data
+        e.alpha_column = -1 if alpha_column is None else int(alpha_column)
+        e.gym_reward = self.GYM_REWARDS[reward]
+        e.reward_shape = self.REWARD_SHAPES[shape]
+        e.dense_target = 0.0 if dense_target is None else float(dense_target)
+        L.check(L.lib().cpr_lane_env_set(self.handle, ctypes.byref(e)))
+        self._lane_env = True
+
+    def lane_alpha(self):
+        """alpha of every lane's current episode (cpr_lane_alpha)."""
+        a = np.zeros(self.n_lanes)
+        L.check(L.lib().cpr_lane_alpha(self.handle, L.ptr(a)))
+        return a
+
     ROLLOUT_NET_OUTPUTS = ("obs0", "obs", "action", "reward", "done", "logp", "value")
+    ROLLOUT_ENV_OUTPUTS = ("alpha0", "alpha", "engine_reward")
+
+    def _rollout_arrays(self, n_steps):
+        n = self.n_lanes
+        return {
+            "obs0": np.zeros((n, self.obs_len)),
+            "obs": np.zeros((n_steps, n, self.obs_len)),
+            "action": np.zeros((n_steps, n), dtype=np.int32),
+            "reward": np.zeros((n_steps, n)),
+            "done": np.zeros((n_steps, n), dtype=np.uint8),
+            "logp": np.zeros((n_steps, n)),
+            "value": np.zeros((n_steps + 1, n)),
+        }
 
     def rollout_net(self, n_steps, deterministic=False, outputs=True, summary=None,
                     device_outputs=None):
@@ -518,32 +572,54 @@ class Batch:
         obs0 [n_lanes, obs_len], obs [n_steps, n_lanes, obs_len], action, reward, done, logp
         [n_steps, n_lanes] and value [n_steps + 1, n_lanes] (row n_steps: the bootstrap value);
         ``device_outputs={name: device pointer}`` (e.g. torch tensors' ``data_ptr()``) writes
-        those buffers on the device instead and returns the same dict."""
+        those buffers on the device instead and returns the same dict.
+
+        With a lane env (``set_lane_env``) the call goes through cpr_rollout_net_env:
+        ``reward`` is the wrapped and shaped reward, and the arrays gain alpha0 [n_lanes],
+        alpha [n_steps, n_lanes] (the alpha of the episode obs0 / obs[t] belongs to) and
+        engine_reward [n_steps, n_lanes] (the unwrapped reward); ``device_outputs`` accepts
+        those names too (with or without a lane env)."""
         n_steps = int(n_steps)
         if n_steps < 1:
             raise ValueError("n_steps: at least 1")
         s = summary if summary is not None else L.Summary()
         n = self.n_lanes
         o = L.RolloutNetOut()
+        eo = L.RolloutEnvOut()
+        det = 1 if deterministic else 0
         if device_outputs is not None:
+            use_env = getattr(self, "_lane_env", False)
             for k, v in device_outputs.items():
-                if k not in self.ROLLOUT_NET_OUTPUTS:
+                if k in self.ROLLOUT_ENV_OUTPUTS:
+                    setattr(eo, k, None if v is None else int(v))
+                    use_env = True
+                elif k in self.ROLLOUT_NET_OUTPUTS:
+                    setattr(o, k, None if v is None else int(v))
+                else:
                     raise ValueError(f"device_outputs: unknown output {k!r}")
-                setattr(o, k, None if v is None else int(v))
-            L.check(L.lib().cpr_rollout_net(self.handle, n_steps, 1 if deterministic else 0,
-                                            ctypes.byref(o), 1, ctypes.byref(s)))
+            if use_env:
+                L.check(L.lib().cpr_rollout_net_env(self.handle, n_steps, det, ctypes.byref(o),
+                                                    ctypes.byref(eo), 1, ctypes.byref(s)))
+            else:
+                L.check(L.lib().cpr_rollout_net(self.handle, n_steps, det, ctypes.byref(o), 1,
+                                                ctypes.byref(s)))
             return s, device_outputs
+        if getattr(self, "_lane_env", False):
+            arrays = {}
+            if outputs:
+                arrays = self._rollout_arrays(n_steps)
+                arrays.update(alpha0=np.zeros(n), alpha=np.zeros((n_steps, n)),
+                              engine_reward=np.zeros((n_steps, n)))
+                for k, v in arrays.items():
+                    setattr(eo if k in self.ROLLOUT_ENV_OUTPUTS else o, k, v.ctypes.data)
+            L.check(L.lib().cpr_rollout_net_env(self.handle, n_steps, det, ctypes.byref(o),
+                                                ctypes.byref(eo), 0, ctypes.byref(s)))
+            if outputs:
+                arrays["done"] = arrays["done"].astype(bool)
+            return s, arrays
         arrays = {}
         if outputs:
-            arrays = {
-                "obs0": np.zeros((n, self.obs_len)),
-                "obs": np.zeros((n_steps, n, self.obs_len)),
-                "action": np.zeros((n_steps, n), dtype=np.int32),
-                "reward": np.zeros((n_steps, n)),
-                "done": np.zeros((n_steps, n), dtype=np.uint8),
-                "logp": np.zeros((n_steps, n)),
-                "value": np.zeros((n_steps + 1, n)),
-            }
+            arrays = self._rollout_arrays(n_steps)
             for k, v in arrays.items():
                 setattr(o, k, v.ctypes.data)
         L.check(L.lib().cpr_rollout_net(self.handle, n_steps, 1 if deterministic else 0,

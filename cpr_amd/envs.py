@@ -151,6 +151,78 @@ def env_fn(
     return env
 
 
+def device_env_fn(
+    n_envs,
+    ctx=None,
+    seed=0,
+    protocol="nakamoto",
+    protocol_args=None,
+    _protocol_args=dict(unit_observation=True),
+    activation_delay=1.0,
+    episode_len=128,
+    alpha=0.45,
+    gamma=0.5,
+    pretend_alpha=None,
+    pretend_gamma=None,
+    defenders=None,
+    reward="sparse_relative",
+    normalize_reward=True,
+    shape=None,
+):
+    """``env_fn`` (cpr-v0) over ``n_envs`` device lanes: returns ``(batch, extras)``, a
+    configured ``device.Batch`` whose lane env (``Batch.set_lane_env``) holds the assumption
+    schedule and the reward wrapper, and the extras tuple of the ``PolicyNet`` that goes with
+    it (``PolicyNet(..., extra=extras)``, then ``batch.rollout_net``).
+
+    Built the way ``env_fn`` builds cpr-v0: max_steps = episode_len for the sparse rewards,
+    max_steps = 100 episode_len and max_progress = episode_len for the dense one, defenders
+    derived from gamma, ``normalize_reward`` -> r / alpha. ``shape`` ("none", "per_alpha",
+    "cut"; ppo.py's raw is "per_alpha") overrides ``normalize_reward``. ``alpha`` is a float,
+    a sequence (one entry is chosen per episode, like ppo.py's ``random.choice``; the
+    reference's wrapper cycles a sequence instead) or a zero-argument callable. Deviation: a
+    callable is sampled 4,096 times into the table here, and episodes choose among those
+    draws by (seed, episode). Gamma is fixed, as in ppo.py."""
+    from . import _lib as L
+    from . import device
+
+    if callable(gamma) or np.ndim(gamma) != 0:
+        raise ValueError("device_env_fn: gamma is fixed per batch (a float)")
+    if callable(alpha):
+        table = [float(alpha()) for _ in range(L.LANE_ENV_MAX_ALPHA)]
+    else:
+        table = [float(a) for a in np.atleast_1d(alpha)]
+    ctor = getattr(protocols, protocol)
+    args = dict(_protocol_args) if protocol_args is None else {**_protocol_args, **protocol_args}
+    proto = ctor(**args)
+    if reward not in ("sparse_relative", "sparse_per_progress", "dense_per_progress"):
+        raise KeyError(reward)
+    dense = reward == "dense_per_progress"
+    if shape is None:
+        shape = "per_alpha" if normalize_reward else "none"
+    cfg, keep = device.make_config(
+        protocol=proto.protocol_id,
+        k=proto.params.get("k", 8),
+        subblock_selection=proto.params.get("selection_id", 1),
+        reward_scheme=proto.params.get("reward_scheme", L.REWARD_CONSTANT),
+        alpha=table[0],
+        gamma=float(gamma),
+        defenders=defenders,
+        policy=L.POLICY_HONEST,
+        activation_delay=activation_delay,
+        max_steps=episode_len * 100 if dense else episode_len,
+        max_progress=episode_len if dense else None,
+        seed=seed,
+        unit_observation=proto.unit_observation,
+        n_lanes=n_envs,
+    )
+    batch = device.Batch(cfg, ctx=ctx, keep=keep)
+    batch.set_lane_env(alphas=table, alpha_column=None if pretend_alpha is not None else 0,
+                       reward=reward, shape=shape, dense_target=episode_len if dense else None)
+    extras = (table[0] if pretend_alpha is None else float(pretend_alpha),
+              float(gamma) if pretend_gamma is None else float(pretend_gamma))
+    return batch, extras
+
+
 _registry = {
     "core-v0": (Core, {}),
     "cpr-v0": (env_fn, {}),

@@ -469,7 +469,7 @@ int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint
  * action head (n_actions of cpr_observation_spec) and a linear value head (1). The input
  * row is the lane's observation converted to f32 followed by the n_extra constants
  * extra[0..n_extra) (the alpha, gamma features of AssumptionScheduleWrapper, constant
- * within a batch). Weights are f32, row-major [out][in] like torch.nn.Linear: layer l of a
+ * within a batch unless cpr_lane_env_set names an alpha column). Weights are f32, row-major [out][in] like torch.nn.Linear: layer l of a
  * trunk is w[l] [width][l == 0 ? obs_len + n_extra : width], b[l] [width]; heads are
  * [n_actions][width_pi] and [1][width_vf]. All host pointers, copied by the call.
  * Arithmetic is f32 in, f32 accumulate on the matrix cores; argmax, sampling and the
@@ -539,6 +539,91 @@ typedef struct cpr_rollout_net_out {
 int cpr_rollout_net(cpr_batch* b, int64_t n_steps, int deterministic,
                     const cpr_rollout_net_out* out, int outputs_on_device,
                     cpr_summary* summary);
+
+/* The gym layers of cpr-v0 over the lockstep lanes (added within v11; a batch on which
+ * cpr_lane_env_set was never called behaves exactly as before). gym/ocaml/cpr_gym/envs.py:99-191
+ * wraps core-v0 in an assumption schedule (an alpha per episode, appended to the observation),
+ * a reward wrapper and a normalisation; experiments/train/ppo.py:105-141,200-270 schedules
+ * alpha per episode and shapes the reward. Here:
+ *
+ * Assumption schedule. The batch holds a table of n_alpha alphas. Episode e runs at entry
+ *   min(n_alpha - 1, (int)(u n_alpha)), u = u53(w0, w1) of the keyed block
+ *   ctr = (e, 0, 0x70000000), key = seed
+ * (random.choice over a list, ppo.py:117-118; a range is served by a table of grid points
+ * or of pre-drawn values): an episode's alpha depends on (seed, episode) only, not on the
+ * lane count or on how a rollout is cut into calls. The table is converted to miner-draw
+ * thresholds like cfg.alpha, so a one-entry table equal to cfg.alpha changes nothing.
+ * Gamma, defenders and delays stay the batch's. The per-lane alpha holds in cpr_reset,
+ * cpr_step, cpr_observe_fields and cpr_rollout_net (the exact-engine continuation of
+ * Nakamoto lanes included). Fused episodes (cpr_run_episodes), cpr_replay and
+ * cpr_node_outputs of the same batch keep cfg.alpha.
+ *
+ * Network input. In a network rollout, extra column alpha_column of the network's input is
+ * the row's lane alpha rounded to f32 instead of the constant extra[alpha_column]; the other
+ * extras stay constants. extra = (alpha, gamma) with alpha_column = 0 is
+ * AssumptionScheduleWrapper's layout (wrappers.py:172-242); alpha_column = -1 leaves every
+ * extra constant (its pretend_alpha). cpr_policy_net_forward works on host rows that belong
+ * to no lane and keeps using the constants.
+ *
+ * Rewards of a network rollout (f64, one rounding per operation, from the step infos):
+ *   CPR_GYM_REWARD_ENGINE              engine.ml:223, unchanged
+ *   CPR_GYM_REWARD_SPARSE_RELATIVE     0 until done, then ra / (ra + rd), 0 if the sum is 0
+ *                                      (wrappers.py:8-26)
+ *   CPR_GYM_REWARD_SPARSE_PER_PROGRESS 0 until done, then ra / progress, 0 if progress is 0
+ *                                      (wrappers.py:29-51)
+ *   CPR_GYM_REWARD_DENSE_PER_PROGRESS  r * (1 / dense_target) per step, summed per lane since
+ *                                      its reset (acc); at a done with progress != dense_target
+ *                                      the reward gains (dense_target - progress) * acc /
+ *                                      progress (wrappers.py:54-113; nothing where progress
+ *                                      is 0: the reference raises there). The accumulator
+ *                                      follows network rollouts and resets only: steps taken
+ *                                      through cpr_step or cpr_rollout are not added
+ * then the shape:
+ *   CPR_SHAPE_NONE       r
+ *   CPR_SHAPE_PER_ALPHA  r / alpha of the lane (envs.py:149-150, ppo.py `raw`)
+ *   CPR_SHAPE_CUT        0 if r <= 0 or progress <= 0; (r * 0.9) / alpha if n_activations /
+ *                        progress <= 1.05; else r / alpha (ppo.py:221-232)
+ * ppo.py's `exp` shape is left to the caller (numpy.exp is not pinned bit for bit): the
+ * unshaped reward and the alpha are among the outputs. cpr_step's reward stays the engine's. */
+enum cpr_gym_reward {
+  CPR_GYM_REWARD_ENGINE = 0,
+  CPR_GYM_REWARD_SPARSE_RELATIVE = 1,
+  CPR_GYM_REWARD_SPARSE_PER_PROGRESS = 2,
+  CPR_GYM_REWARD_DENSE_PER_PROGRESS = 3
+};
+enum cpr_reward_shape { CPR_SHAPE_NONE = 0, CPR_SHAPE_PER_ALPHA = 1, CPR_SHAPE_CUT = 2 };
+#define CPR_LANE_ENV_MAX_ALPHA 4096
+typedef struct cpr_lane_env {
+  int32_t n_alpha;       /* 1..CPR_LANE_ENV_MAX_ALPHA table entries; 0 with alpha = NULL: */
+  const double* alpha;   /* cfg.alpha for every lane. Host pointer, copied by the call */
+  int32_t alpha_column;  /* extras column fed with the lane's alpha; -1 none */
+  int32_t gym_reward;    /* enum cpr_gym_reward */
+  int32_t reward_shape;  /* enum cpr_reward_shape */
+  double dense_target;   /* CPR_GYM_REWARD_DENSE_PER_PROGRESS: episode_len (> 0) */
+} cpr_lane_env;
+/* Set the batch's lane env, before its first reset or rollout (CPR_E_STATE afterwards).
+ * CPR_E_INVALID_ARG: n_alpha out of range; an alpha that is NaN or outside [0, 1], or outside
+ * (0, 1] with a shape that divides by it; dense_target <= 0 with the dense reward;
+ * alpha_column < -1, or >= n_extra of the batch's network (checked by whichever of this call
+ * and cpr_policy_net_set comes second). CPR_E_UNSUPPORTED: FC16, a batch without lockstep
+ * lanes. While a table is set (n_alpha > 0), cpr_rollout (built-in policies) is
+ * CPR_E_UNSUPPORTED. */
+int cpr_lane_env_set(cpr_batch* b, const cpr_lane_env* env);
+/* alpha of every lane's current episode ([n_lanes], host): cfg.alpha without a lane env or
+ * before the first reset; the Python wrappers' info["alpha"] */
+int cpr_lane_alpha(cpr_batch* b, double* alpha);
+/* further outputs of a network rollout; every pointer optional */
+typedef struct cpr_rollout_env_out {
+  double* alpha0;        /* [n_lanes] alpha of the episode obs0 belongs to */
+  double* alpha;         /* [n_steps][n_lanes] alpha of the episode obs[t] belongs to */
+  double* engine_reward; /* [n_steps][n_lanes] the unwrapped engine.ml:223 reward */
+} cpr_rollout_env_out;
+/* cpr_rollout_net with those outputs (env_out may be NULL: the same call). Once a lane env
+ * is set, out->reward of either call is the wrapped and shaped reward. cpr_summary is
+ * computed as before. */
+int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
+                        const cpr_rollout_net_out* out, const cpr_rollout_env_out* env_out,
+                        int outputs_on_device, cpr_summary* summary);
 
 /* policy evaluated on encoded observations (host): obs n x obs_len -> actions n */
 int cpr_policy_actions(cpr_batch* b, int32_t policy, const double* obs, int64_t n,

@@ -260,6 +260,18 @@ let rollout_net =
     (ptr batch @-> int64_t @-> int @-> ptr void @-> int @-> ptr summary @-> returning int)
 ;;
 
+(* the gym layers of cpr-v0 over the lanes (added within ABI v11): cpr_lane_env and
+   cpr_rollout_env_out are untyped pointers to caller-built C structs as well *)
+let lane_env_set = foreign "cpr_lane_env_set" (ptr batch @-> ptr void @-> returning int)
+let lane_alpha = foreign "cpr_lane_alpha" (ptr batch @-> ptr double @-> returning int)
+
+let rollout_net_env =
+  foreign
+    "cpr_rollout_net_env"
+    (ptr batch @-> int64_t @-> int @-> ptr void @-> ptr void @-> int @-> ptr summary
+    @-> returning int)
+;;
+
 let policy_actions =
   foreign
     "cpr_policy_actions"

@@ -8,6 +8,7 @@ Layout (DESIGN.md):
   protocols.py drop-in for the reference's `protocols` module (cpr_gym_engine.ml:165-304)
   envs.py      Core env, env_fn and registered ids (gym/ocaml/cpr_gym/envs.py)
   wrappers.py  reward / assumption wrappers (gym/ocaml/cpr_gym/wrappers.py)
+  ppo.py       the learner's options, flat parameter order and training loop (cpr_ppo_*)
   parallel.py  one process per GPU, episode sharding, RCCL all-reduce of batch summaries
 """
 

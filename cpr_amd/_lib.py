@@ -291,6 +291,63 @@ class RolloutEnvOut(ctypes.Structure):
     ]
 
 
+class PpoOptsC(ctypes.Structure):
+    """cpr_ppo_opts (include/cpr_hip.h)."""
+
+    _fields_ = [
+        ("n_epochs", ctypes.c_int32),
+        ("minibatch", ctypes.c_int64),
+        ("clip_range", ctypes.c_double),
+        ("ent_coef", ctypes.c_double),
+        ("vf_coef", ctypes.c_double),
+        ("max_grad_norm", ctypes.c_double),
+        ("lr", ctypes.c_double),
+        ("beta1", ctypes.c_double),
+        ("beta2", ctypes.c_double),
+        ("adam_eps", ctypes.c_double),
+        ("normalize_advantage", ctypes.c_int32),
+        ("gae_gamma", ctypes.c_double),
+        ("gae_lambda", ctypes.c_double),
+        ("perm_seed", ctypes.c_uint64),
+    ]
+
+
+class PpoDataC(ctypes.Structure):
+    """cpr_ppo_data: n rows of training data, host or device pointers."""
+
+    _fields_ = [
+        ("n", ctypes.c_int64),
+        ("obs", ctypes.c_void_p),
+        ("alpha", ctypes.c_void_p),
+        ("action", ctypes.c_void_p),
+        ("old_logp", ctypes.c_void_p),
+        ("advantage", ctypes.c_void_p),
+        ("ret", ctypes.c_void_p),
+        ("on_device", ctypes.c_int32),
+    ]
+
+
+class PpoStats(ctypes.Structure):
+    """cpr_ppo_stats: SB3's logged statistics of a minibatch or an update."""
+
+    _fields_ = [
+        ("policy_loss", ctypes.c_double),
+        ("value_loss", ctypes.c_double),
+        ("entropy_loss", ctypes.c_double),
+        ("approx_kl", ctypes.c_double),
+        ("clip_fraction", ctypes.c_double),
+        ("loss", ctypes.c_double),
+        ("grad_norm", ctypes.c_double),
+        ("n_minibatches", ctypes.c_int64),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+TAG_PERM = 0x80000000  # keyed-stream tag of cpr_ppo_update's permutations
+
+
 class CTrace(ctypes.Structure):
     _fields_ = [
         ("n_episodes", ctypes.c_int64),
@@ -411,6 +468,13 @@ EXPORTS = [
     "cpr_lane_env_set",
     "cpr_lane_alpha",
     "cpr_rollout_net_env",
+    "cpr_gae",
+    "cpr_ppo_opts_default",
+    "cpr_ppo_gradients",
+    "cpr_ppo_param_count",
+    "cpr_ppo_update",
+    "cpr_ppo_iterate",
+    "cpr_policy_net_get",
     "cpr_policy_actions",
     "cpr_observation_spec",
     "cpr_policy_count",
@@ -463,6 +527,15 @@ def _declare(L):
     L.cpr_lane_alpha.argtypes = [vp, vp]
     L.cpr_rollout_net_env.argtypes = [vp, ctypes.c_int64, ctypes.c_int, P(RolloutNetOut),
                                       P(RolloutEnvOut), ctypes.c_int, P(Summary)]
+    L.cpr_gae.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp,
+                          ctypes.c_int]
+    L.cpr_ppo_opts_default.argtypes = [P(PpoOptsC)]
+    L.cpr_ppo_gradients.argtypes = [vp, P(PpoDataC), vp, ctypes.c_int64, P(PpoOptsC), vp,
+                                    P(PpoStats)]
+    L.cpr_ppo_param_count.argtypes = [vp, P(ctypes.c_int64)]
+    L.cpr_ppo_update.argtypes = [vp, P(PpoDataC), P(PpoOptsC), vp, P(PpoStats)]
+    L.cpr_ppo_iterate.argtypes = [vp, ctypes.c_int64, P(PpoOptsC), P(Summary), P(PpoStats)]
+    L.cpr_policy_net_get.argtypes = [vp, P(PolicyNetC)]
     L.cpr_policy_actions.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int64, vp]
     L.cpr_observation_spec.argtypes = [vp, P(ctypes.c_int32), P(ctypes.c_int32), vp, vp]
     L.cpr_policy_count.argtypes = [ctypes.c_int32]

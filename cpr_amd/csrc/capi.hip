@@ -18,6 +18,7 @@
 #include "lane_env.h"
 #include "nak_hybrid.h"
 #include "policy_net.h"
+#include "ppo.h"
 
 using namespace cpr;
 
@@ -193,6 +194,18 @@ struct cpr_batch {
   cpr_lane_env env = {};  // n_alpha >= 1 once set (cfg.alpha alone without a table)
   bool env_table = false; // the caller gave a table: cpr_rollout is refused
   DevBuf le_tab_t, le_tab_a, le_lane_t, le_lane_a, le_acc;
+  // the learner (cpr_ppo_*): where each parameter array stands in pn_w (floats, arrays padded
+  // to 4) and its length, in the flat gradient's order; Adam's moments and step count; the
+  // number of updates since the network was set (the permutation's counter); per-minibatch
+  // scratch; staging of host data; cpr_ppo_iterate's rollout buffers
+  std::vector<int64_t> pn_off, pn_cnt;
+  int64_t pn_total = 0;
+  int64_t ppo_t = 0, ppo_updates = 0;
+  DevBuf pp_m, pp_v, pp_grad, pp_part, pp_xin, pp_act, pp_dy0, pp_dy1, pp_dlg, pp_dv, pp_advn,
+      pp_partial, pp_stats, pp_red, pp_bpart, pp_idx, pp_perm;
+  DevBuf pp_obs, pp_alpha, pp_action, pp_logp, pp_adv, pp_ret;
+  std::vector<int32_t> perm_host;
+  DevBuf it_obs, it_alpha, it_action, it_reward, it_done, it_logp, it_value, it_adv, it_ret;
   bool reset_done = false;
   int32_t tab_n = 4096;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -2434,6 +2447,16 @@ int cpr_policy_net_set(cpr_batch* b, const cpr_policy_net* net) {
   HIP_TRY(b->pn_w.ensure(host.size() * sizeof(float)));
   HIP_TRY(hipMemcpy(b->pn_w.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
   for (size_t i = 0; i < arrs.size(); i++) *arrs[i].dst = (const float*)b->pn_w.p + offs[i];
+  // the learner's view of the buffer; Adam starts over with a new network
+  b->pn_off = offs;
+  b->pn_cnt.clear();
+  for (const Arr& a : arrs) b->pn_cnt.push_back(a.count);
+  b->pn_total = (int64_t)host.size();
+  b->ppo_t = 0;
+  b->ppo_updates = 0;
+  if (b->pp_m.p) HIP_TRY(hipMemsetAsync(b->pp_m.p, 0, b->pp_m.bytes, b->ctx->stream));
+  if (b->pp_v.p) HIP_TRY(hipMemsetAsync(b->pp_v.p, 0, b->pp_v.bytes, b->ctx->stream));
+  b->pp_part.release();  // its zeroed padding stood where the previous network's was
   b->pn = N;
   b->has_net = true;
   return CPR_OK;
@@ -2758,6 +2781,521 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
   summary->status_other += s.status_other;
   summary->invalid += s.invalid;
   for (int i = 0; i < CPR_HIST_BINS; i++) summary->hist[i] += s.hist[i];
+  return CPR_OK;
+}
+
+// ---------------------------------------------------------------- the learner (ppo.h)
+
+int cpr_gae(cpr_batch* b, int64_t n_steps, const double* reward, const uint8_t* done,
+            const double* value, double gamma, double lam, double* adv_out, double* ret_out,
+            int on_device) {
+  if (!b || !reward || !done || !value || !adv_out || !ret_out)
+    return fail(CPR_E_INVALID_ARG, "NULL argument");
+  const int64_t n = b->cfg.n_lanes;
+  if (n <= 0) return fail(CPR_E_UNSUPPORTED, "gae needs lockstep lanes (cfg.n_lanes > 0)");
+  if (n_steps < 1) return fail(CPR_E_INVALID_ARG, "gae: n_steps must be >= 1");
+  if (!std::isfinite(gamma) || !std::isfinite(lam))
+    return fail(CPR_E_INVALID_ARG, "gae: non-finite gamma or lambda");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  hipStream_t st = b->ctx->stream;
+  const size_t cells = (size_t)(n_steps * n);
+  if (on_device) {
+    HIP_TRY(launch_gae(n_steps, n, reward, done, value, gamma, lam, adv_out, ret_out, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CPR_OK;
+  }
+  DevBuf r, d, v, a, q;
+  HIP_TRY(r.ensure(cells * 8));
+  HIP_TRY(d.ensure(cells));
+  HIP_TRY(v.ensure((cells + (size_t)n) * 8));
+  HIP_TRY(a.ensure(cells * 8));
+  HIP_TRY(q.ensure(cells * 8));
+  HIP_TRY(hipMemcpyAsync(r.p, reward, cells * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d.p, done, cells, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(v.p, value, (cells + (size_t)n) * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(launch_gae(n_steps, n, (const double*)r.p, (const uint8_t*)d.p, (const double*)v.p,
+                     gamma, lam, (double*)a.p, (double*)q.p, st));
+  HIP_TRY(hipMemcpyAsync(adv_out, a.p, cells * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(ret_out, q.p, cells * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CPR_OK;
+}
+
+int cpr_ppo_opts_default(cpr_ppo_opts* o) {
+  if (!o) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  *o = cpr_ppo_opts{};
+  o->n_epochs = 10;
+  o->minibatch = 64;
+  o->clip_range = 0.1;
+  o->ent_coef = 0.0;
+  o->vf_coef = 0.5;
+  o->max_grad_norm = 0.5;
+  o->lr = 3e-4;
+  o->beta1 = 0.9;
+  o->beta2 = 0.999;
+  o->adam_eps = 1e-5;
+  o->normalize_advantage = 1;
+  o->gae_gamma = 0.99;
+  o->gae_lambda = 0.95;
+  o->perm_seed = 0;
+  return CPR_OK;
+}
+
+// state, shapes and options of every cpr_ppo_* call, before anything is launched
+static int ppo_check(cpr_batch* b, const cpr_ppo_opts* o) {
+  if (!b || !o) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (b->cfg.protocol == CPR_PROTO_FC16)
+    return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
+  if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
+  if (o->n_epochs < 1) return fail(CPR_E_INVALID_ARG, "ppo: n_epochs must be >= 1");
+  if (o->minibatch < 1) return fail(CPR_E_INVALID_ARG, "ppo: minibatch must be >= 1");
+  if (o->minibatch > INT32_MAX) return fail(CPR_E_INVALID_ARG, "ppo: minibatch above 2^31 - 1");
+  const struct {
+    const char* name;
+    double v;
+    bool positive;
+  } fields[] = {{"clip_range", o->clip_range, true},      {"ent_coef", o->ent_coef, false},
+                {"vf_coef", o->vf_coef, false},           {"max_grad_norm", o->max_grad_norm, true},
+                {"lr", o->lr, false},                     {"beta1", o->beta1, false},
+                {"beta2", o->beta2, false},               {"adam_eps", o->adam_eps, false},
+                {"gae_gamma", o->gae_gamma, false},       {"gae_lambda", o->gae_lambda, false}};
+  for (const auto& f : fields) {
+    if (!std::isfinite(f.v)) return fail(CPR_E_INVALID_ARG, std::string("ppo: non-finite ") + f.name);
+    if (f.positive && !(f.v > 0.0))
+      return fail(CPR_E_INVALID_ARG, std::string("ppo: ") + f.name + " must be > 0");
+  }
+  if (!(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0))
+    return fail(CPR_E_INVALID_ARG, "ppo: beta1 and beta2 must be in [0, 1)");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  const int64_t lds = ppo_lds_bytes(b->pn.depth, b->pn.width_pi, b->pn.width_vf);
+  if (lds > ppo_lds_limit())
+    return fail(CPR_E_UNSUPPORTED,
+                "ppo: the training forward of this network needs " + std::to_string(lds) +
+                    " B of LDS per workgroup, the device has " + std::to_string(ppo_lds_limit()));
+  return CPR_OK;
+}
+
+// the training data on the device: the caller's pointers, or staged copies
+struct PpoDev {
+  int64_t n;
+  const double* obs;
+  const double* alpha;  // null unless the lane env feeds an alpha column
+  int32_t alpha_col;
+  const int32_t* action;
+  const double* old_logp;
+  const double* adv;
+  const double* ret;
+};
+
+static int ppo_stage(cpr_batch* b, const cpr_ppo_data* d, PpoDev* out) {
+  if (!d) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (d->n < 1) return fail(CPR_E_INVALID_ARG, "ppo: data.n must be >= 1");
+  if (d->n > INT32_MAX) return fail(CPR_E_INVALID_ARG, "ppo: data.n above 2^31 - 1 (int32 rows)");
+  if (!d->obs || !d->action || !d->old_logp || !d->advantage || !d->ret)
+    return fail(CPR_E_INVALID_ARG, "ppo: NULL data array");
+  const bool use_alpha = b->has_env && b->env.alpha_column >= 0;
+  if (use_alpha && !d->alpha)
+    return fail(CPR_E_INVALID_ARG, "ppo: data.alpha is NULL but the lane env names an alpha column");
+  PpoDev D = {};
+  D.n = d->n;
+  D.alpha_col = use_alpha ? b->env.alpha_column : -1;
+  if (d->on_device) {
+    D.obs = d->obs;
+    D.alpha = use_alpha ? d->alpha : nullptr;
+    D.action = d->action;
+    D.old_logp = d->old_logp;
+    D.adv = d->advantage;
+    D.ret = d->ret;
+    *out = D;
+    return CPR_OK;
+  }
+  const size_t n = (size_t)d->n;
+  const int na = b->pn.n_actions;
+  for (size_t i = 0; i < n; i++)
+    if (d->action[i] < 0 || d->action[i] >= na)
+      return fail(CPR_E_INVALID_ARG, "ppo: data.action out of range");
+  hipStream_t st = b->ctx->stream;
+  struct {
+    DevBuf* buf;
+    const void* src;
+    size_t bytes;
+  } cp[] = {{&b->pp_obs, d->obs, n * (size_t)b->pn.obs_len * 8},
+            {&b->pp_alpha, use_alpha ? d->alpha : nullptr, n * 8},
+            {&b->pp_action, d->action, n * 4},
+            {&b->pp_logp, d->old_logp, n * 8},
+            {&b->pp_adv, d->advantage, n * 8},
+            {&b->pp_ret, d->ret, n * 8}};
+  for (auto& c : cp) {
+    if (!c.src) continue;
+    HIP_TRY(c.buf->ensure(c.bytes));
+    HIP_TRY(hipMemcpyAsync(c.buf->p, c.src, c.bytes, hipMemcpyHostToDevice, st));
+  }
+  D.obs = (const double*)b->pp_obs.p;
+  D.alpha = use_alpha ? (const double*)b->pp_alpha.p : nullptr;
+  D.action = (const int32_t*)b->pp_action.p;
+  D.old_logp = (const double*)b->pp_logp.p;
+  D.adv = (const double*)b->pp_adv.p;
+  D.ret = (const double*)b->pp_ret.p;
+  *out = D;
+  return CPR_OK;
+}
+
+// rows of the weight gradient's row blocks for a minibatch of B rows: at most
+// kPpoMaxRowBlocks blocks, each a multiple of 64 rows
+static int32_t ppo_rows_per_block(int64_t B) {
+  const int64_t per = (B + kPpoMaxRowBlocks - 1) / kPpoMaxRowBlocks;
+  return (int32_t)(((per + 63) / 64) * 64);
+}
+
+// scratch of minibatches of up to B rows
+static int ppo_scratch(cpr_batch* b, int64_t B) {
+  const PolNet& N = b->pn;
+  const size_t rows = (size_t)B;
+  const size_t wmax = (size_t)std::max(N.width_pi, N.width_vf);
+  const size_t total = (size_t)b->pn_total;
+  hipStream_t st = b->ctx->stream;
+  if (b->pp_m.bytes < total * 4) {  // first use, or a larger network was set (ppo_t is 0)
+    HIP_TRY(b->pp_m.ensure(total * 4));
+    HIP_TRY(b->pp_v.ensure(total * 4));
+    HIP_TRY(hipMemsetAsync(b->pp_m.p, 0, b->pp_m.bytes, st));
+    HIP_TRY(hipMemsetAsync(b->pp_v.p, 0, b->pp_v.bytes, st));
+  }
+  HIP_TRY(b->pp_grad.ensure(total * 4));
+  // the arrays' padding is never written by k_ppo_dw: zero once, so that the summed gradient,
+  // the moments and the weights keep zeros there
+  const size_t part = total * 4 * kPpoMaxRowBlocks;
+  if (b->pp_part.bytes < part) {
+    HIP_TRY(b->pp_part.ensure(part));
+    HIP_TRY(hipMemsetAsync(b->pp_part.p, 0, part, st));
+  }
+  size_t biases = 0;
+  for (size_t k = 1; k < b->pn_cnt.size(); k += 2) biases += (size_t)b->pn_cnt[k];
+  HIP_TRY(b->pp_bpart.ensure(biases * 8 * kPpoMaxRowBlocks));
+  HIP_TRY(b->pp_xin.ensure(rows * kPolInStride * 4));
+  HIP_TRY(b->pp_act.ensure(rows * (size_t)N.depth * (size_t)(N.width_pi + N.width_vf) * 4));
+  HIP_TRY(b->pp_dy0.ensure(2 * rows * wmax * 4));
+  HIP_TRY(b->pp_dy1.ensure(2 * rows * wmax * 4));
+  HIP_TRY(b->pp_dlg.ensure(rows * (size_t)N.n_actions * 4));
+  HIP_TRY(b->pp_dv.ensure(rows * 4));
+  HIP_TRY(b->pp_advn.ensure(rows * 8));
+  HIP_TRY(b->pp_partial.ensure(((rows + kPolRows - 1) / kPolRows) * kPpoRowStats * 8));
+  HIP_TRY(b->pp_stats.ensure(2 * kPpoStats * 8));  // the minibatch's, then the update's sums
+  HIP_TRY(b->pp_red.ensure(3 * kPpoRedBlocks * 8));  // partials of the f64 reductions
+  return CPR_OK;
+}
+
+// the gradient of minibatch idx[0 .. B) into pp_grad and its statistics into pp_stats (added
+// to acc if given); launches only
+static int ppo_minibatch(cpr_batch* b, const PpoDev& D, const int32_t* idx, int64_t B,
+                         const cpr_ppo_opts& o, double* acc) {
+  const PolNet& N = b->pn;
+  hipStream_t st = b->ctx->stream;
+  double* stats = (double*)b->pp_stats.p;
+  double* red = (double*)b->pp_red.p;
+  HIP_TRY(launch_adv_norm(D.adv, idx, B, D.n, o.normalize_advantage, red, (double*)b->pp_advn.p, st));
+  PpoFwd F = {};
+  F.obs = D.obs;
+  F.alpha = D.alpha;
+  F.alpha_col = D.alpha_col;
+  F.action = D.action;
+  F.old_logp = D.old_logp;
+  F.ret = D.ret;
+  F.advn = (const double*)b->pp_advn.p;
+  F.idx = idx;
+  F.B = B;
+  F.N = D.n;
+  F.clip = o.clip_range;
+  F.ent_coef = o.ent_coef;
+  F.vf_coef = o.vf_coef;
+  F.xin = (float*)b->pp_xin.p;
+  float* ap = (float*)b->pp_act.p;
+  for (int trunk = 0; trunk < 2; trunk++)
+    for (int l = 0; l < N.depth; l++) {
+      F.act[trunk][l] = ap;
+      ap += (size_t)B * (size_t)(trunk == 0 ? N.width_pi : N.width_vf);
+    }
+  F.dlogits = (float*)b->pp_dlg.p;
+  F.dvalue = (float*)b->pp_dv.p;
+  F.partial = (double*)b->pp_partial.p;
+  HIP_TRY(launch_ppo_forward(N, F, st));
+  const int64_t blocks = (B + kPolRows - 1) / kPolRows;
+  HIP_TRY(launch_ppo_stats(F.partial, blocks, B, o.ent_coef, o.vf_coef, stats, acc, st));
+  // backward, from each head down; both trunks' layer l in one launch
+  PpoBwd P = {};
+  P.B = B;
+  P.rows_per_block = ppo_rows_per_block(B);
+  P.part = (float*)b->pp_part.p;
+  P.pstride = b->pn_total;
+  // the biases alone, in array order: their partials are f64
+  PpoBiasMap M = {};
+  M.arrays = 2 * (N.depth + 1);
+  for (int k = 0; k < M.arrays; k++) {
+    M.off[k] = b->pn_off[2 * k + 1];
+    M.start[k + 1] = M.start[k] + b->pn_cnt[2 * k + 1];
+  }
+  P.bpart = (double*)b->pp_bpart.p;
+  P.bstride = M.start[M.arrays];
+  const size_t wmax = (size_t)std::max(N.width_pi, N.width_vf);
+  float* dy[2] = {(float*)b->pp_dy0.p, (float*)b->pp_dy1.p};
+  const float* cur[2] = {F.dlogits, F.dvalue};
+  int32_t ld[2] = {N.n_actions, 1};
+  for (int l = N.depth; l >= 0; l--) {
+    float* out = dy[(N.depth - l) & 1];
+    for (int trunk = 0; trunk < 2; trunk++) {
+      const PolLayer& Ly = trunk == 0 ? N.pi[l] : N.vf[l];
+      PpoBwdJob& J = P.j[trunk];
+      J.dY = cur[trunk];
+      J.ldy = ld[trunk];
+      J.X = l == 0 ? F.xin : F.act[trunk][l - 1];
+      J.ldx = l == 0 ? kPolInStride : Ly.n_in;
+      J.W = Ly.W;
+      J.n_out = Ly.n_out;
+      J.n_in = Ly.n_in;
+      J.dX = l == 0 ? nullptr : out + (size_t)trunk * (size_t)B * wmax;
+      const size_t a = (size_t)trunk * (size_t)(N.depth + 1) * 2 + (size_t)l * 2;
+      J.off_w = b->pn_off[a];
+      J.off_b = b->pn_off[a + 1];
+      J.off_bc = M.start[a / 2];
+    }
+    HIP_TRY(launch_ppo_dw(P, st));
+    if (l > 0) {
+      HIP_TRY(launch_ppo_dx(P, st));
+      for (int trunk = 0; trunk < 2; trunk++) {
+        cur[trunk] = P.j[trunk].dX;
+        ld[trunk] = P.j[trunk].n_in;
+      }
+    }
+  }
+  const int32_t rb = (int32_t)((B + P.rows_per_block - 1) / P.rows_per_block);
+  HIP_TRY(launch_ppo_reduce(P.part, P.pstride, rb, b->pn_total, (float*)b->pp_grad.p, st));
+  HIP_TRY(launch_ppo_reduce_bias(P.bpart, P.bstride, rb, M, (float*)b->pp_grad.p, st));
+  HIP_TRY(launch_grad_norm((const float*)b->pp_grad.p, b->pn_total, red + 2 * kPpoRedBlocks, stats,
+                           acc, st));
+  return CPR_OK;
+}
+
+static void ppo_stats_out(const double* s, double div, int64_t count, cpr_ppo_stats* out) {
+  out->policy_loss = s[kPpoPolicyLoss] / div;
+  out->value_loss = s[kPpoValueLoss] / div;
+  out->entropy_loss = s[kPpoEntropyLoss] / div;
+  out->approx_kl = s[kPpoApproxKl] / div;
+  out->clip_fraction = s[kPpoClipFraction] / div;
+  out->loss = s[kPpoLoss] / div;
+  out->grad_norm = s[kPpoGradNorm] / div;
+  out->n_minibatches = count;
+}
+
+int cpr_ppo_param_count(cpr_batch* b, int64_t* count) {
+  if (!b || !count) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
+  int64_t c = 0;
+  for (int64_t k : b->pn_cnt) c += k;
+  *count = c;
+  return CPR_OK;
+}
+
+int cpr_ppo_gradients(cpr_batch* b, const cpr_ppo_data* data, const int32_t* rows_idx,
+                      int64_t n_rows, const cpr_ppo_opts* opts, float* grad_out,
+                      cpr_ppo_stats* stats_out) {
+  int rc = ppo_check(b, opts);
+  if (rc) return rc;
+  if (!rows_idx || !grad_out) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (n_rows < 1 || n_rows > INT32_MAX)
+    return fail(CPR_E_INVALID_ARG, "ppo: n_rows must be in 1 .. 2^31 - 1");
+  PpoDev D;
+  rc = ppo_stage(b, data, &D);
+  if (rc) return rc;
+  hipStream_t st = b->ctx->stream;
+  const int32_t* idx = rows_idx;
+  if (!data->on_device) {
+    for (int64_t i = 0; i < n_rows; i++)
+      if (rows_idx[i] < 0 || rows_idx[i] >= D.n)
+        return fail(CPR_E_INVALID_ARG, "ppo: rows_idx out of range");
+    HIP_TRY(b->pp_idx.ensure((size_t)n_rows * 4));
+    HIP_TRY(hipMemcpyAsync(b->pp_idx.p, rows_idx, (size_t)n_rows * 4, hipMemcpyHostToDevice, st));
+    idx = (const int32_t*)b->pp_idx.p;
+  }
+  rc = ppo_scratch(b, n_rows);
+  if (rc) return rc;
+  rc = ppo_minibatch(b, D, idx, n_rows, *opts, nullptr);
+  if (rc) return rc;
+  float* g = grad_out;
+  for (size_t i = 0; i < b->pn_cnt.size(); i++) {
+    HIP_TRY(hipMemcpyAsync(g, (const float*)b->pp_grad.p + b->pn_off[i], (size_t)b->pn_cnt[i] * 4,
+                           hipMemcpyDeviceToHost, st));
+    g += b->pn_cnt[i];
+  }
+  double s[kPpoStats];
+  HIP_TRY(hipMemcpyAsync(s, b->pp_stats.p, sizeof(s), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (stats_out) ppo_stats_out(s, 1.0, 1, stats_out);
+  return CPR_OK;
+}
+
+// epoch e's permutation of 0 .. n - 1 (include/cpr_hip.h cpr_ppo_update)
+constexpr uint32_t TAG_PERM = 0x80000000u;
+static void ppo_draw_perm(uint64_t seed, uint64_t perm_seed, uint64_t update, uint32_t epoch,
+                          int64_t n, int32_t* p) {
+  const uint64_t key = seed ^ (perm_seed * 0x9E3779B97F4A7C15ull);
+  for (int64_t i = 0; i < n; i++) p[i] = (int32_t)i;
+  Words4 w = {};
+  int64_t have = -1;
+  for (int64_t i = n - 1; i >= 1; i--) {
+    if (have != (i >> 1)) {
+      have = i >> 1;
+      w = philox4x32_10((uint32_t)update, epoch, (uint32_t)have, TAG_PERM, (uint32_t)key,
+                        (uint32_t)(key >> 32));
+    }
+    const double u = (i & 1) ? u53(w.w2, w.w3) : u53(w.w0, w.w1);
+    int64_t j = (int64_t)(u * (double)(i + 1));
+    if (j > i) j = i;
+    std::swap(p[i], p[j]);
+  }
+}
+
+int cpr_ppo_update(cpr_batch* b, const cpr_ppo_data* data, const cpr_ppo_opts* opts,
+                   const int32_t* perm, cpr_ppo_stats* stats_out) {
+  int rc = ppo_check(b, opts);
+  if (rc) return rc;
+  PpoDev D;
+  rc = ppo_stage(b, data, &D);
+  if (rc) return rc;
+  const cpr_ppo_opts& o = *opts;
+  hipStream_t st = b->ctx->stream;
+  const int64_t n = D.n;
+  const size_t cells = (size_t)o.n_epochs * (size_t)n;
+  const int32_t* pd = perm;
+  if (!perm || !data->on_device) {
+    if (perm) {
+      for (size_t i = 0; i < cells; i++)
+        if (perm[i] < 0 || perm[i] >= n) return fail(CPR_E_INVALID_ARG, "ppo: perm out of range");
+    } else {
+      // drawn here, uploaded behind the kernels already queued; perm_host stays until the
+      // synchronisation at the end of this call
+      b->perm_host.resize(cells);
+      for (int32_t e = 0; e < o.n_epochs; e++)
+        ppo_draw_perm(b->cfg.seed, o.perm_seed, (uint64_t)b->ppo_updates, (uint32_t)e, n,
+                      b->perm_host.data() + (size_t)e * (size_t)n);
+    }
+    HIP_TRY(b->pp_perm.ensure(cells * 4));
+    HIP_TRY(hipMemcpyAsync(b->pp_perm.p, perm ? perm : b->perm_host.data(), cells * 4,
+                           hipMemcpyHostToDevice, st));
+    pd = (const int32_t*)b->pp_perm.p;
+  }
+  const int64_t mb = std::min<int64_t>(o.minibatch, n);
+  rc = ppo_scratch(b, mb);
+  if (rc) return rc;
+  double* acc = (double*)b->pp_stats.p + kPpoStats;
+  HIP_TRY(hipMemsetAsync(acc, 0, kPpoStats * 8, st));
+  int64_t count = 0;
+  for (int32_t e = 0; e < o.n_epochs; e++)
+    for (int64_t s0 = 0; s0 < n; s0 += mb) {
+      const int64_t B = std::min<int64_t>(mb, n - s0);
+      rc = ppo_minibatch(b, D, pd + (size_t)e * (size_t)n + s0, B, o, acc);
+      if (rc) return rc;
+      const double t = (double)++b->ppo_t;
+      PpoAdam A = {};
+      A.p = (float*)b->pn_w.p;
+      A.g = (const float*)b->pp_grad.p;
+      A.m = (float*)b->pp_m.p;
+      A.v = (float*)b->pp_v.p;
+      A.n = b->pn_total;
+      A.stats = (const double*)b->pp_stats.p;
+      A.max_norm = (float)o.max_grad_norm;
+      A.b1 = (float)o.beta1;
+      A.omb1 = (float)(1.0 - o.beta1);
+      A.b2 = (float)o.beta2;
+      A.omb2 = (float)(1.0 - o.beta2);
+      A.step = (float)(o.lr / (1.0 - std::pow(o.beta1, t)));
+      A.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(o.beta2, t));
+      A.eps = (float)o.adam_eps;
+      HIP_TRY(launch_adam(A, st));
+      ++count;
+    }
+  double s[kPpoStats];
+  HIP_TRY(hipMemcpyAsync(s, acc, sizeof(s), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  ++b->ppo_updates;
+  if (stats_out) ppo_stats_out(s, (double)count, count, stats_out);
+  return CPR_OK;
+}
+
+int cpr_ppo_iterate(cpr_batch* b, int64_t n_steps, const cpr_ppo_opts* opts,
+                    cpr_summary* summary, cpr_ppo_stats* stats_out) {
+  int rc = ppo_check(b, opts);
+  if (rc) return rc;
+  if (!summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (n_steps < 1) return fail(CPR_E_INVALID_ARG, "ppo: n_steps must be >= 1");
+  const int64_t n = b->cfg.n_lanes;
+  if (n_steps * n > INT32_MAX)
+    return fail(CPR_E_INVALID_ARG, "ppo: n_steps * n_lanes above 2^31 - 1 (int32 rows)");
+  const size_t cells = (size_t)(n_steps * n);
+  const size_t ol = (size_t)obs_len_of(b->cfg);
+  // obs0 and obs share one buffer, so that the policy input of flat row r is its row r; the
+  // same for the alphas
+  HIP_TRY(b->it_obs.ensure((cells + (size_t)n) * ol * 8));
+  HIP_TRY(b->it_alpha.ensure((cells + (size_t)n) * 8));
+  HIP_TRY(b->it_action.ensure(cells * 4));
+  HIP_TRY(b->it_reward.ensure(cells * 8));
+  HIP_TRY(b->it_done.ensure(cells));
+  HIP_TRY(b->it_logp.ensure(cells * 8));
+  HIP_TRY(b->it_value.ensure((cells + (size_t)n) * 8));
+  HIP_TRY(b->it_adv.ensure(cells * 8));
+  HIP_TRY(b->it_ret.ensure(cells * 8));
+  cpr_rollout_net_out out = {};
+  out.obs0 = (double*)b->it_obs.p;
+  out.obs = out.obs0 + (size_t)n * ol;
+  out.action = (int32_t*)b->it_action.p;
+  out.reward = (double*)b->it_reward.p;
+  out.done = (uint8_t*)b->it_done.p;
+  out.logp = (double*)b->it_logp.p;
+  out.value = (double*)b->it_value.p;
+  cpr_rollout_env_out eo = {};
+  eo.alpha0 = (double*)b->it_alpha.p;
+  eo.alpha = eo.alpha0 + n;
+  rc = cpr_rollout_net_env(b, n_steps, 0, &out, &eo, 1, summary);
+  if (rc) return rc;
+  rc = cpr_gae(b, n_steps, out.reward, out.done, out.value, opts->gae_gamma, opts->gae_lambda,
+               (double*)b->it_adv.p, (double*)b->it_ret.p, 1);
+  if (rc) return rc;
+  cpr_ppo_data d = {};
+  d.n = (int64_t)cells;
+  d.obs = out.obs0;
+  d.alpha = eo.alpha0;
+  d.action = out.action;
+  d.old_logp = out.logp;
+  d.advantage = (const double*)b->it_adv.p;
+  d.ret = (const double*)b->it_ret.p;
+  d.on_device = 1;
+  return cpr_ppo_update(b, &d, opts, nullptr, stats_out);
+}
+
+int cpr_policy_net_get(cpr_batch* b, cpr_policy_net* net) {
+  if (!b || !net) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
+  const PolNet& N = b->pn;
+  std::vector<float*> dst;
+  for (int trunk = 0; trunk < 2; trunk++) {
+    for (int l = 0; l < N.depth; l++) {
+      dst.push_back((float*)(trunk == 0 ? net->pi_w[l] : net->vf_w[l]));
+      dst.push_back((float*)(trunk == 0 ? net->pi_b[l] : net->vf_b[l]));
+    }
+    dst.push_back((float*)(trunk == 0 ? net->pi_head_w : net->vf_head_w));
+    dst.push_back((float*)(trunk == 0 ? net->pi_head_b : net->vf_head_b));
+  }
+  for (float* p : dst)
+    if (!p) return fail(CPR_E_INVALID_ARG, "policy net: NULL weight or bias array");
+  net->n_extra = N.n_extra;
+  for (int i = 0; i < N.n_extra; i++) net->extra[i] = N.extra[i];
+  net->depth = N.depth;
+  net->width_pi = N.width_pi;
+  net->width_vf = N.width_vf;
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  hipStream_t st = b->ctx->stream;
+  for (size_t i = 0; i < dst.size(); i++)
+    HIP_TRY(hipMemcpyAsync(dst[i], (const float*)b->pn_w.p + b->pn_off[i], (size_t)b->pn_cnt[i] * 4,
+                           hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return CPR_OK;
 }
 

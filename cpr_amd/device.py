@@ -261,6 +261,27 @@ class PolicyNet:
                    vf=trunk("mlp_extractor.value_net."),
                    vf_head=(sd["value_net.weight"], sd["value_net.bias"]), extra=extra)
 
+    def state_dict(self):
+        """{name: f32 array} in SB3's ActorCriticPolicy naming: the inverse of
+        ``from_state_dict`` (wrap the arrays in ``torch.from_numpy`` for ``load_state_dict``)."""
+        sd = {}
+        for prefix, trunk in (("mlp_extractor.policy_net.", self.pi),
+                              ("mlp_extractor.value_net.", self.vf)):
+            for i, (w, b) in enumerate(trunk):
+                sd[f"{prefix}{2 * i}.weight"] = w
+                sd[f"{prefix}{2 * i}.bias"] = b
+        sd["action_net.weight"], sd["action_net.bias"] = self.pi_head
+        sd["value_net.weight"], sd["value_net.bias"] = self.vf_head
+        return sd
+
+    def zeros_like(self):
+        """A network of the same shape and extras with zeroed parameters."""
+        def z(wb):
+            return np.zeros_like(wb[0]), np.zeros_like(wb[1])
+
+        return PolicyNet([z(x) for x in self.pi], z(self.pi_head), [z(x) for x in self.vf],
+                         z(self.vf_head), extra=self.extra)
+
     def cstruct(self):
         """The cpr_policy_net over this object's arrays (which must outlive the call)."""
         c = L.PolicyNetC()
@@ -627,6 +648,146 @@ class Batch:
         if outputs:
             arrays["done"] = arrays["done"].astype(bool)
         return s, arrays
+
+    # ---- the learner (cpr_gae, cpr_ppo_*; DESIGN.md §4.14 "Learner")
+    def gae(self, reward, done, value, gamma=0.99, lam=0.95, device=False, n_steps=None,
+            out=None):
+        """SB3's compute_returns_and_advantage over step-major buffers (cpr_gae): reward, done
+        [n_steps, n_lanes], value [n_steps + 1, n_lanes] -> (advantage, return) arrays. With
+        ``device=True`` the three are device pointers (ints, e.g. torch tensors'
+        ``data_ptr()``), ``n_steps`` is given and the result goes to the device pointers
+        ``out=(advantage, return)``."""
+        if device:
+            if n_steps is None or out is None:
+                raise ValueError("gae: device=True needs n_steps and out=(adv_ptr, ret_ptr)")
+            ptrs = [ctypes.c_void_p(int(x)) for x in (reward, done, value, out[0], out[1])]
+            L.check(L.lib().cpr_gae(self.handle, int(n_steps), ptrs[0], ptrs[1], ptrs[2],
+                                    float(gamma), float(lam), ptrs[3], ptrs[4], 1))
+            return out
+        r = np.ascontiguousarray(reward, dtype=np.float64)
+        d = np.ascontiguousarray(done, dtype=np.uint8)
+        v = np.ascontiguousarray(value, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != self.n_lanes or d.shape != r.shape or \
+                v.shape != (r.shape[0] + 1, r.shape[1]):
+            raise ValueError(f"gae: expected reward, done [n_steps, {self.n_lanes}] and value "
+                             f"[n_steps + 1, {self.n_lanes}]")
+        adv, ret = np.zeros_like(r), np.zeros_like(r)
+        L.check(L.lib().cpr_gae(self.handle, r.shape[0], L.ptr(r), L.ptr(d), L.ptr(v), float(gamma),
+                                float(lam), L.ptr(adv), L.ptr(ret), 0))
+        return adv, ret
+
+    PPO_DATA = ("obs", "alpha", "action", "old_logp", "advantage", "ret")
+
+    def _ppo_data(self, data, device):
+        """(cpr_ppo_data, the arrays it points to) of a dict with the keys of PPO_DATA
+        (``alpha`` optional): host arrays, or with ``device=True`` device pointers and ``n``."""
+        c = L.PpoDataC()
+        if device:
+            c.n = int(data["n"])
+            for k in self.PPO_DATA:
+                v = data.get(k)
+                setattr(c, k, None if v is None else int(v))
+            c.on_device = 1
+            return c, None
+        dt = {"obs": np.float64, "alpha": np.float64, "action": np.int32, "old_logp": np.float64,
+              "advantage": np.float64, "ret": np.float64}
+        keep = {}
+        for k in self.PPO_DATA:
+            v = data.get(k)
+            if v is None:
+                if k != "alpha":
+                    raise ValueError(f"data: {k!r} is missing")
+                continue
+            keep[k] = np.ascontiguousarray(v, dtype=dt[k])
+        n = keep["action"].size
+        keep["obs"] = keep["obs"].reshape(-1, self.obs_len)
+        for k, v in keep.items():
+            if v.shape[0] != n or (k != "obs" and v.ndim != 1):
+                raise ValueError(f"data: {k!r} has shape {list(v.shape)}, expected {n} rows")
+            setattr(c, k, v.ctypes.data)
+        c.n = n
+        c.on_device = 0
+        return c, keep
+
+    @staticmethod
+    def _ppo_opts(options):
+        from .ppo import PPOOptions
+
+        o = options if options is not None else PPOOptions()
+        for name in ("minibatch", "n_epochs"):
+            if int(getattr(o, name)) < 1:
+                raise ValueError(f"{name}: at least 1")
+        for name in ("lr", "clip_range"):
+            if not math.isfinite(float(getattr(o, name))):
+                raise ValueError(f"{name}: non-finite value")
+        return o.cstruct()
+
+    def ppo_param_count(self):
+        n = ctypes.c_int64()
+        L.check(L.lib().cpr_ppo_param_count(self.handle, ctypes.byref(n)))
+        return n.value
+
+    def ppo_gradients(self, data, rows, options=None, device=False):
+        """The PPO gradient of the minibatch ``rows`` (int32 indices into ``data``; a device
+        pointer and ``data["n_rows"]`` with ``device=True``) without touching the weights:
+        (flat f32 gradient in ``cpr_amd.ppo.param_arrays`` order, statistics dict)."""
+        o = self._ppo_opts(options)
+        c, keep = self._ppo_data(data, device)
+        if device:
+            idx, n_rows = ctypes.c_void_p(int(rows)), int(data["n_rows"])
+        else:
+            ia = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+            idx, n_rows = L.ptr(ia), ia.size
+        grad = np.zeros(self.ppo_param_count(), dtype=np.float32)
+        st = L.PpoStats()
+        L.check(L.lib().cpr_ppo_gradients(self.handle, ctypes.byref(c), idx, n_rows,
+                                          ctypes.byref(o), L.ptr(grad), ctypes.byref(st)))
+        del keep
+        return grad, st.as_dict()
+
+    def ppo_update(self, data, options=None, perm=None, device=False):
+        """n_epochs x ceil(n / minibatch) steps of gradient, clip and Adam on the batch's device
+        weights (cpr_ppo_update). ``perm``: int32 [n_epochs, n] (a device pointer with
+        ``device=True``), or None for the library's keyed permutations. Returns the update's
+        statistics dict (means over the minibatches)."""
+        o = self._ppo_opts(options)
+        c, keep = self._ppo_data(data, device)
+        pa = None
+        if perm is None:
+            pp = None
+        elif device:
+            pp = ctypes.c_void_p(int(perm))
+        else:
+            pa = np.ascontiguousarray(perm, dtype=np.int32)
+            if pa.shape != (o.n_epochs, c.n):
+                raise ValueError(f"perm: expected [{o.n_epochs}, {c.n}], got {list(pa.shape)}")
+            pp = L.ptr(pa)
+        st = L.PpoStats()
+        L.check(L.lib().cpr_ppo_update(self.handle, ctypes.byref(c), ctypes.byref(o), pp,
+                                       ctypes.byref(st)))
+        del keep, pa
+        return st.as_dict()
+
+    def ppo_iterate(self, n_steps, options=None, summary=None):
+        """One PPO iteration on the device (cpr_ppo_iterate): a sampled network rollout of
+        ``n_steps`` into buffers the batch owns, GAE, the update. Returns (summary of the
+        rollout, statistics dict of the update)."""
+        o = self._ppo_opts(options)
+        s = summary if summary is not None else L.Summary()
+        st = L.PpoStats()
+        L.check(L.lib().cpr_ppo_iterate(self.handle, int(n_steps), ctypes.byref(o), ctypes.byref(s),
+                                        ctypes.byref(st)))
+        return s, st.as_dict()
+
+    def get_policy_net(self):
+        """The batch's current weights as a ``PolicyNet`` (cpr_policy_net_get)."""
+        net = getattr(self, "_net", None)
+        if net is None:
+            raise L.CprError(L.CPR_E_STATE, "no policy network set (set_policy_net)")
+        out = net.zeros_like()
+        c = out.cstruct()
+        L.check(L.lib().cpr_policy_net_get(self.handle, ctypes.byref(c)))
+        return out
 
     def observation_spec(self):
         ol = ctypes.c_int32()

@@ -625,6 +625,101 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
                         const cpr_rollout_net_out* out, const cpr_rollout_env_out* env_out,
                         int outputs_on_device, cpr_summary* summary);
 
+/* The learner (added within v11; a batch that never calls these launches what it did before):
+ * SB3's PPO.train (experiments/train/ppo.py:399-451) on the batch's device weights.
+ * DESIGN.md §4.14 "Learner" has the loss, its derivative and every reduction order.
+ *
+ * cpr_gae: RolloutBuffer.compute_returns_and_advantage over step-major f64 buffers of the
+ * batch's n_lanes: reward, done [n_steps][n_lanes], value [n_steps + 1][n_lanes] (row n_steps
+ * the bootstrap) -> adv_out, ret_out [n_steps][n_lanes]. Per lane, t = n_steps - 1 .. 0, one
+ * rounding per operation:
+ *   nnt = 1 - done[t];  delta = (reward[t] + (gamma value[t + 1]) nnt) - value[t]
+ *   last = delta + ((gamma lam) nnt) last;  adv[t] = last;  ret[t] = last + value[t]
+ * (value[t + 1] at a done step is the reset observation's value, masked by nnt; no
+ * time-limit bootstrap). Host pointers, or device pointers if on_device != 0. */
+int cpr_gae(cpr_batch* b, int64_t n_steps, const double* reward, const uint8_t* done,
+            const double* value, double gamma, double lam, double* adv_out, double* ret_out,
+            int on_device);
+
+typedef struct cpr_ppo_opts {
+  int32_t n_epochs;            /* >= 1 */
+  int64_t minibatch;           /* >= 1 rows; an epoch's last minibatch may be shorter */
+  double clip_range;
+  double ent_coef;
+  double vf_coef;
+  double max_grad_norm;
+  double lr;                   /* per call: the caller applies its schedule */
+  double beta1, beta2, adam_eps;
+  int32_t normalize_advantage; /* per minibatch, (A - mean) / (std + 1e-8), unbiased std */
+  double gae_gamma, gae_lambda; /* cpr_ppo_iterate */
+  uint64_t perm_seed;
+} cpr_ppo_opts;
+/* the reference's values (ppo.py:399-417 over SB3's defaults): 10 epochs, minibatch 64,
+ * clip 0.1, ent 0, vf 0.5, max-norm 0.5, lr 3e-4, betas (0.9, 0.999), eps 1e-5, normalised
+ * advantages, gamma 0.99, lambda 0.95, perm_seed 0 */
+int cpr_ppo_opts_default(cpr_ppo_opts* opts);
+
+/* n rows of training data (the flat [n_steps * n_lanes] rollout buffers): the policy input of
+ * every row, its lane alpha (read only when the batch's lane env names an alpha column), the
+ * action taken, its log-probability then, the advantage and the return. Host pointers, or
+ * device pointers if on_device != 0; rows_idx / perm of the calls below follow the same flag. */
+typedef struct cpr_ppo_data {
+  int64_t n;
+  const double* obs;       /* [n][obs_len] */
+  const double* alpha;     /* [n] or NULL */
+  const int32_t* action;   /* [n] */
+  const double* old_logp;  /* [n] */
+  const double* advantage; /* [n] */
+  const double* ret;       /* [n] */
+  int32_t on_device;
+} cpr_ppo_data;
+
+/* SB3's logged statistics: row means of a minibatch, or their mean over an update's minibatches */
+typedef struct cpr_ppo_stats {
+  double policy_loss;   /* mean(-min(A rho, A clamp(rho, 1 - c, 1 + c))) */
+  double value_loss;    /* mean((R - v)^2) */
+  double entropy_loss;  /* mean(-H) */
+  double approx_kl;     /* mean((rho - 1) - log rho) */
+  double clip_fraction; /* mean(|rho - 1| > c) */
+  double loss;          /* policy_loss + ent_coef entropy_loss + vf_coef value_loss */
+  double grad_norm;     /* global L2 norm before the clip */
+  int64_t n_minibatches;
+} cpr_ppo_stats;
+
+/* The gradient of one minibatch (rows rows_idx[0 .. n_rows) of data, int32) and its statistics;
+ * the weights stay. grad_out (host): a flat f32 vector, for the pi trunk then the vf trunk:
+ * each hidden layer's W [out][in] then b, then the head's W and b -- cpr_ppo_param_count
+ * floats. stats_out may be NULL. Synchronous. CPR_E_STATE without a network;
+ * CPR_E_UNSUPPORTED if the training kernels' tile exceeds the device's LDS (refused before
+ * any launch); CPR_E_INVALID_ARG names the offending field. */
+int cpr_ppo_gradients(cpr_batch* b, const cpr_ppo_data* data, const int32_t* rows_idx,
+                      int64_t n_rows, const cpr_ppo_opts* opts, float* grad_out,
+                      cpr_ppo_stats* stats_out);
+int cpr_ppo_param_count(cpr_batch* b, int64_t* count);
+
+/* n_epochs x ceil(n / minibatch) steps of gradient, global-norm clip and Adam on the batch's
+ * device weights, no host synchronisation between them. perm: int32 [n_epochs][n], each row a
+ * permutation of 0 .. n - 1 (minibatch k of epoch e is perm[e][k minibatch ..]). perm == NULL:
+ * the library draws epoch e's permutation by Fisher-Yates from the keyed stream,
+ *   for i = n - 1 .. 1: swap(p[i], p[min(i, (int)(u (i + 1)))]), u = u53 of words 2 (i & 1), + 1
+ *   of block ctr = (update count, e, i >> 1, 0x80000000), key = seed ^ perm_seed * 0x9E3779B97F4A7C15
+ * where the update count is the number of cpr_ppo_update calls on this batch since
+ * cpr_policy_net_set. Adam's m, v and step count belong to the batch and are zeroed by
+ * cpr_policy_net_set. stats_out (optional): means over the minibatches. Synchronous. */
+int cpr_ppo_update(cpr_batch* b, const cpr_ppo_data* data, const cpr_ppo_opts* opts,
+                   const int32_t* perm, cpr_ppo_stats* stats_out);
+
+/* One PPO iteration: cpr_rollout_net_env (sampled) of n_steps into rollout buffers the batch
+ * owns on the device, cpr_gae (opts->gae_gamma, gae_lambda), cpr_ppo_update (perm NULL) on the
+ * n_steps * n_lanes rows. Bit for bit what the three calls give when composed by hand. */
+int cpr_ppo_iterate(cpr_batch* b, int64_t n_steps, const cpr_ppo_opts* opts,
+                    cpr_summary* summary, cpr_ppo_stats* stats_out);
+
+/* The batch's current weights into the caller's arrays, laid out as for cpr_policy_net_set
+ * (every array pointer of `net` must be writable despite the const; n_extra, extra, depth
+ * and the widths are filled in). */
+int cpr_policy_net_get(cpr_batch* b, cpr_policy_net* net);
+
 /* policy evaluated on encoded observations (host): obs n x obs_len -> actions n */
 int cpr_policy_actions(cpr_batch* b, int32_t policy, const double* obs, int64_t n,
                        int32_t* actions);

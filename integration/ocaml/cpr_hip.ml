@@ -272,6 +272,42 @@ let rollout_net_env =
     @-> returning int)
 ;;
 
+(* the learner (added within ABI v11): cpr_ppo_opts, cpr_ppo_data and cpr_ppo_stats are
+   untyped pointers to caller-built C structs (include/cpr_hip.h) *)
+let gae =
+  foreign
+    "cpr_gae"
+    (ptr batch @-> int64_t @-> ptr double @-> ptr uint8_t @-> ptr double @-> double @-> double
+    @-> ptr double @-> ptr double @-> int @-> returning int)
+;;
+
+let ppo_opts_default = foreign "cpr_ppo_opts_default" (ptr void @-> returning int)
+
+let ppo_gradients =
+  foreign
+    "cpr_ppo_gradients"
+    (ptr batch @-> ptr void @-> ptr int32_t @-> int64_t @-> ptr void @-> ptr float @-> ptr void
+    @-> returning int)
+;;
+
+let ppo_param_count =
+  foreign "cpr_ppo_param_count" (ptr batch @-> ptr int64_t @-> returning int)
+;;
+
+let ppo_update =
+  foreign
+    "cpr_ppo_update"
+    (ptr batch @-> ptr void @-> ptr void @-> ptr int32_t @-> ptr void @-> returning int)
+;;
+
+let ppo_iterate =
+  foreign
+    "cpr_ppo_iterate"
+    (ptr batch @-> int64_t @-> ptr void @-> ptr summary @-> ptr void @-> returning int)
+;;
+
+let policy_net_get = foreign "cpr_policy_net_get" (ptr batch @-> ptr void @-> returning int)
+
 let policy_actions =
   foreign
     "cpr_policy_actions"

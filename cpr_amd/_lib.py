@@ -89,6 +89,11 @@ ST_LOCKSTEP_INEXACT = ST_OVERLAP | ST_DEEP_FORK | ST_TIE_UNRESOLVED | ST_STALE_T
 ABI_VERSION = 11  # include/cpr_hip.h CPR_ABI_VERSION this module's structures follow
 
 HIST_BINS = 64
+# largest group of sweep points one fused lane runs at gamma = 0 and with deferred races
+# (csrc/nak_fused.h CPR_NAK_FUSE_MAX, CPR_NAK_FUSE_MAX_ARR; only the tests read them, and
+# tests/test_gpu_fused_points.py test_group_sizes* fail if the library groups otherwise)
+NAK_FUSE_MAX = 5
+NAK_FUSE_MAX_ARR = 2
 
 
 class Config(ctypes.Structure):

@@ -119,6 +119,28 @@ struct cpr_ctx {
   hipEvent_t list_ev[2] = {nullptr, nullptr};
   bool list_pending[2] = {false, false};
   int list_i = 0;
+  // cpr_run_episodes_async calls not launched yet: sweep points that share
+  // seed, first episode, episode count and every parameter but alpha, to run in one lane of
+  // k_run_episodes_fused. Launched by fuse_launch_pending, which every entry point calls first
+  struct FuseMember {
+    cpr_batch* b;
+    cpr_summary* sum;
+  };
+  std::vector<FuseMember> fuse;
+  int fuse_kind = 0;  // run_episodes_fusable of the members
+  int64_t fuse_n = 0;
+  uint64_t fuse_first = 0;
+};
+
+// the HIP events around a fused group's kernel, shared by its members (cpr_last_launch: the
+// group's time divided by its size)
+struct FuseTime {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int size = 1;
+  ~FuseTime() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
 };
 
 static hipError_t side_join(cpr_ctx* c) {
@@ -169,6 +191,7 @@ struct cpr_batch {
   eth::EthParams NEP;    // the Ethereum lane in Nakamoto mode
   int64_t nak_bytes = 0;
   bool async_launch = false;  // last launch came from cpr_run_episodes_async
+  std::shared_ptr<FuseTime> fuse_time;  // ... as a member of a fused group (else null)
   std::vector<uint8_t> table_host;
   DevBuf table_dev, tabs_dev;  // policy table; unit-observation tables
   DevBuf summary, records;
@@ -229,6 +252,15 @@ int cpr_device_count(int* out) {
 }
 
 static int flush_reruns(cpr_ctx* c);
+// Launches the context's pending group of deferred cpr_run_episodes_async calls, if any. At
+// the top of every entry point that takes a context or a batch (CPR_ENTER), so that whatever
+// the entry does comes after the launches the caller has already asked for; an error of the
+// deferred launch is returned by that entry
+static int fuse_launch_pending(cpr_ctx* c);
+#define CPR_ENTER(ctx_)                                             \
+  do {                                                              \
+    if (const int rc_ = fuse_launch_pending(ctx_)) return rc_;      \
+  } while (0)
 
 int cpr_ctx_create(int device, cpr_ctx** out) {
   if (!out) return fail(CPR_E_INVALID_ARG, "out is NULL");
@@ -256,6 +288,7 @@ int cpr_ctx_create(int device, cpr_ctx** out) {
 
 int cpr_ctx_destroy(cpr_ctx* c) {
   if (!c) return CPR_OK;
+  (void)fuse_launch_pending(c);
   (void)hipSetDevice(c->device);
   // pending work first: queued exact re-runs complete their callers' summaries and records
   (void)flush_reruns(c);  // joins the side stream's second passes first
@@ -285,6 +318,7 @@ int cpr_ctx_destroy(cpr_ctx* c) {
 }
 
 int cpr_synchronize(cpr_ctx* c) {
+  CPR_ENTER(c);
   HIP_TRY(hipSetDevice(c->device));
   int rc = flush_reruns(c);  // joins the side stream first
   if (rc) return rc;
@@ -788,6 +822,7 @@ static int validate_ts(const cpr_config* c, ts::TsParams* P) {
 
 int cpr_batch_create(cpr_ctx* ctx, const cpr_config* cfg, cpr_batch** out) {
   if (!ctx || !cfg || !out) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(ctx);
   NakParams P;
   eth::EthParams EP;
   bk::BkParams BP;
@@ -894,6 +929,7 @@ static int64_t batch_resident(cpr_batch* b) {
 
 int cpr_launch_shape(cpr_batch* b, int64_t* lanes, int64_t* resident) {
   if (!b) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   HIP_TRY(hipSetDevice(b->ctx->device));
   if (lanes) *lanes = b->last_lanes;
   if (resident) *resident = b->last_lanes ? b->last_resident : batch_resident(b);
@@ -902,6 +938,7 @@ int cpr_launch_shape(cpr_batch* b, int64_t* lanes, int64_t* resident) {
 
 int cpr_rerun_hbm_retries(cpr_ctx* c, int64_t* retries) {
   if (!c || !retries) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(c);
   *retries = 0;
   if (!c->rq.p) return CPR_OK;
   HIP_TRY(hipSetDevice(c->device));
@@ -941,6 +978,7 @@ static int drain_flush_recs(cpr_ctx* c, bool wait) {
 
 int cpr_rerun_stats(cpr_ctx* c, int64_t* episodes, int64_t* flushes, double* ms) {
   if (!c) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(c);
   HIP_TRY(hipSetDevice(c->device));
   if (const int rc = drain_flush_recs(c, true)) return rc;
   if (episodes) *episodes = c->rr_episodes;
@@ -951,6 +989,7 @@ int cpr_rerun_stats(cpr_ctx* c, int64_t* episodes, int64_t* flushes, double* ms)
 
 int cpr_lockstep_coverage(cpr_batch* b, int64_t* log_steps, int64_t* exact_slots) {
   if (!b) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (log_steps) *log_steps = b->l_alog.p ? b->alog_cap : 0;
   if (exact_slots) *exact_slots = b->l_alog.p ? b->n_exact_slots : 0;
   return CPR_OK;
@@ -958,9 +997,19 @@ int cpr_lockstep_coverage(cpr_batch* b, int64_t* log_steps, int64_t* exact_slots
 
 int cpr_last_launch(cpr_batch* b, double* kernel_ms, int64_t* activations) {
   if (!b) return fail(CPR_E_INVALID_ARG, "NULL argument");
-  if (b->async_launch) {  // cpr_run_episodes_async: the caller has synchronized
+  CPR_ENTER(b->ctx);
+  if (b->async_launch) {  // cpr_run_episodes_async: waits for the end of that launch
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+    if (b->fuse_time) {
+      // a member of a fused group: its share of the group's kernel
+      HIP_TRY(hipEventSynchronize(b->fuse_time->ev1));
+      HIP_TRY(hipEventElapsedTime(&ms, b->fuse_time->ev0, b->fuse_time->ev1));
+      ms /= (float)b->fuse_time->size;
+      b->fuse_time.reset();
+    } else {
+      HIP_TRY(hipEventSynchronize(b->ev1));
+      HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+    }
     b->last_ms = ms;
     b->last_acts = -1;  // not known without reading the caller's device summary
     b->async_launch = false;
@@ -972,6 +1021,7 @@ int cpr_last_launch(cpr_batch* b, double* kernel_ms, int64_t* activations) {
 
 int cpr_batch_destroy(cpr_batch* b) {
   if (!b) return CPR_OK;
+  (void)fuse_launch_pending(b->ctx);  // this batch may be a member
   (void)hipSetDevice(b->ctx->device);
   (void)hipStreamSynchronize(b->ctx->stream);
   (void)flush_reruns(b->ctx);  // pending re-runs may read this batch's buffers
@@ -997,9 +1047,9 @@ int cpr_batch_destroy(cpr_batch* b) {
 constexpr int64_t kRerunLanes = 512;
 constexpr int64_t kRerunLanesMax = 8192;  // one workgroup per queued episode, up to this
 
-static int64_t episode_lanes(cpr_batch* b, int64_t n_eps, bool recs) {
-  const int64_t full =
-      (int64_t)b->ctx->cus * run_episodes_blocks_per_cu(b->P, b->cfg.mode, recs) * 256;
+// blocks_per_cu: of the kernel the launch runs
+static int64_t episode_lanes(cpr_batch* b, int64_t n_eps, int blocks_per_cu) {
+  const int64_t full = (int64_t)b->ctx->cus * blocks_per_cu * 256;
   const int64_t budget = (int64_t)(16ll << 30) / episode_lane_bytes(b->P);
   int64_t lanes = std::min(full, std::max<int64_t>(256, budget));
   // A/B: a share of the resident grid (percent), e.g. for launches that run concurrently
@@ -1100,6 +1150,34 @@ static int flush_reruns(cpr_ctx* c) {
   c->ovf_chunk = 0;  // the next launches' flags follow these re-runs on the stream
   c->ovf_used = 0;
   return CPR_OK;
+}
+
+// Whether `count` launches of n_eps episodes can register (register_rerun) one after the
+// other without any of them forcing a flush: room in the launch table, the queue capacity as
+// it stands, and overflow flags for all of them in the chunks that are there or may still be
+// added. (The same walk over the chunks as register_rerun's.)
+static bool rerun_room(const cpr_ctx* c, int64_t n_eps, int count) {
+  int64_t cap = kRerunQueue;
+  if (const char* v = getenv("CPR_RERUN_QUEUE_CAP"))
+    cap = std::max<int64_t>(0, std::min<int64_t>(kRerunQueue, atoll(v)));
+  if (cap != c->rq_cap && !c->rlaunch.empty()) return false;
+  if (c->rlaunch.size() + (size_t)count > kRerunMaxLaunches) return false;
+  const size_t need = align256((size_t)std::max<int64_t>(1, n_eps));
+  const size_t fresh = std::max(need, (size_t)256 << 20);  // a chunk added for this need
+  size_t chunk = c->ovf_chunk, used = c->ovf_used, chunks = c->ovf.size();
+  for (int i = 0; i < count; ++i) {
+    while (chunk < chunks &&
+           used + need > (chunk < c->ovf.size() ? c->ovf[chunk]->bytes : fresh)) {
+      ++chunk;
+      used = 0;
+    }
+    if (chunk == chunks) {
+      if (chunks >= kOvfMaxChunks) return false;
+      ++chunks;
+    }
+    used += need;
+  }
+  return true;
 }
 
 // A launch whose flagged episodes the exact event engine re-runs at the next
@@ -1313,16 +1391,33 @@ static int run_async_fc16(cpr_batch* b, int64_t n, uint64_t first, const TraceSo
   return CPR_OK;
 }
 
+// whether the exact re-runs of this batch's flagged episodes are hybrid ones (see run_async),
+// and the closed form's parameters for them
+static bool rerun_hybrid(const cpr_batch* b, bool trace, NakParams* NP) {
+  const char* hv = getenv("CPR_RERUN_HYBRID");
+  const bool hyb = !(hv && hv[0] == '0') && !trace && b->cfg.mode == CPR_MODE_GYM &&
+                   b->cfg.network == CPR_NET_SELFISH_MINING && b->P.arrive == 1 &&
+                   !b->P.abstract_g && b->cfg.policy != CPR_POLICY_RANDOM &&
+                   !(b->P.max_progress < __builtin_inf()) &&
+                   !(b->P.max_time < __builtin_inf()) &&
+                   b->NEP.max_steps < (1 << 20) &&
+                   b->NEP.max_steps + 2 <= (int64_t)b->NEP.cap_b;
+  *NP = b->P;
+  NP->cap = (int32_t)((b->NEP.max_steps + 2 + 63) / 64 * 64);
+  return hyb;
+}
+
 static int run_async(cpr_batch* b, int64_t n, uint64_t first, const TraceSource* tr,
                      cpr_summary* sum_dev, cpr_episode_record* rec_dev) {
   if (b->cfg.protocol == CPR_PROTO_FC16) return run_async_fc16(b, n, first, tr, sum_dev, rec_dev);
   if (b->cfg.protocol == CPR_PROTO_ETHEREUM || b->nak_ev)
     return run_async_eth(b, n, first, tr, sum_dev, rec_dev);
   if (b->is_ev) return run_async_bk(b, n, first, tr, sum_dev, rec_dev);
-  const int64_t lanes = episode_lanes(b, n, rec_dev != nullptr);
+  const int bpc = run_episodes_blocks_per_cu(b->P, b->cfg.mode, rec_dev != nullptr);
+  const int64_t lanes = episode_lanes(b, n, bpc);
   b->last_lanes = lanes;
-  b->last_resident =
-      (int64_t)b->ctx->cus * run_episodes_blocks_per_cu(b->P, b->cfg.mode, rec_dev != nullptr) * 256;
+  b->last_resident = (int64_t)b->ctx->cus * bpc * 256;
+  b->fuse_time.reset();
   // spill [lane][cap] f64 mining times | tie-replay scratch [lane] | the deferred-race
   // kernel's second-pass list (1 + n words)
   const size_t o_replay = align256((size_t)lanes * b->P.cap * sizeof(double));
@@ -1365,16 +1460,8 @@ static int run_async(cpr_batch* b, int64_t n, uint64_t first, const TraceSource*
     // gym episodes on the selfish-mining network whose attacker messages arrive (gamma > 0),
     // ended by max_steps alone, the whole episode in the engine's block ring, a seeded
     // stream and a deterministic policy; CPR_RERUN_HYBRID=0 re-runs whole episodes (A/B)
-    const char* hv = getenv("CPR_RERUN_HYBRID");
-    const bool hyb = !(hv && hv[0] == '0') && !tr && b->cfg.mode == CPR_MODE_GYM &&
-                     b->cfg.network == CPR_NET_SELFISH_MINING && b->P.arrive == 1 &&
-                     !b->P.abstract_g && b->cfg.policy != CPR_POLICY_RANDOM &&
-                     !(b->P.max_progress < __builtin_inf()) &&
-                     !(b->P.max_time < __builtin_inf()) &&
-                     b->NEP.max_steps < (1 << 20) &&
-                     b->NEP.max_steps + 2 <= (int64_t)b->NEP.cap_b;
-    NakParams NP = b->P;
-    NP.cap = (int32_t)((b->NEP.max_steps + 2 + 63) / 64 * 64);
+    NakParams NP;
+    const bool hyb = rerun_hybrid(b, tr != nullptr, &NP);
     const int rc = register_rerun(b, b->NEP, b->nak_bytes, first, tr, rec_dev, sum_dev, n,
                                   &redo, &redo_n, &launch_id, &ovf, hyb ? &NP : nullptr);
     if (rc) return rc;
@@ -1408,11 +1495,167 @@ static int run_async(cpr_batch* b, int64_t n, uint64_t first, const TraceSource*
   return CPR_OK;
 }
 
+// ---- sweep points that share their draws: one k_run_episodes_fused launch per group
+
+// the largest group (CPR_NAK_FUSE, read at every call; 0 or 1: every call launches at once)
+#ifndef CPR_NAK_FUSE_DEFAULT
+#define CPR_NAK_FUSE_DEFAULT CPR_NAK_FUSE_MAX
+#endif
+#ifndef CPR_NAK_FUSE_DEFAULT_ARR  // the deferred-race (gamma = .5) kernel's
+#define CPR_NAK_FUSE_DEFAULT_ARR CPR_NAK_FUSE_MAX_ARR
+#endif
+static int fuse_cap(int kind) {
+  int cap = kind == 2 ? CPR_NAK_FUSE_DEFAULT_ARR : CPR_NAK_FUSE_DEFAULT;
+  if (const char* v = getenv("CPR_NAK_FUSE")) cap = atoi(v);
+  return std::max(0, std::min(cap, kind == 2 ? kFuseMaxArr : kFuseMax));
+}
+
+// which of the instantiations the fused kernel stands for a call would run (0: neither)
+static int fuse_kind(const cpr_batch* b, const cpr_episode_record* rec_dev) {
+  if (b->cfg.protocol != CPR_PROTO_NAKAMOTO || b->nak_ev || b->is_ev || b->is_eth) return 0;
+  const int kind = run_episodes_fusable(b->P, b->cfg.mode, rec_dev != nullptr);
+  // the deferred-race group's second passes run on the side stream only (CPR_SIDE_PASS=0:
+  // every call launches at once, its second pass on the stream)
+  const char* sp = getenv("CPR_SIDE_PASS");
+  return kind == 2 && sp && sp[0] == '0' ? 0 : kind;
+}
+
+// the same launch but for alpha: every field the kernel and the launcher read except t_att,
+// the seed, and what the exact re-runs of flagged episodes depend on
+static bool fuse_same_launch(const cpr_batch* a, const cpr_batch* b) {
+  const NakParams &P = a->P, &Q = b->P;
+  return a->ctx == b->ctx && a->cfg.seed == b->cfg.seed && a->cfg.mode == b->cfg.mode &&
+         a->cfg.network == b->cfg.network && a->cfg.policy == b->cfg.policy &&
+         P.policy == Q.policy && P.d == Q.d && P.arrive == Q.arrive && P.ev == Q.ev &&
+         P.delta == Q.delta && P.dmax == Q.dmax && P.max_steps == Q.max_steps &&
+         P.max_progress == Q.max_progress && P.max_time == Q.max_time && P.cap == Q.cap &&
+         P.abstract_g == Q.abstract_g && a->has_rerun == b->has_rerun &&
+         a->nak_bytes == b->nak_bytes && a->NEP.max_steps == b->NEP.max_steps &&
+         a->NEP.cap_b == b->NEP.cap_b && a->NEP.cap_e == b->NEP.cap_e && a->NEP.n == b->NEP.n;
+}
+
+static int fuse_launch_pending(cpr_ctx* c) {
+  if (c->fuse.empty()) return CPR_OK;
+  // emptied first: whatever fails below, the group is not launched twice
+  std::vector<cpr_ctx::FuseMember> g;
+  g.swap(c->fuse);
+  const int64_t n = c->fuse_n;
+  const uint64_t first = c->fuse_first;
+  HIP_TRY(hipSetDevice(c->device));
+  const int na = (int)g.size();
+  if (na == 1) {
+    g[0].b->async_launch = true;
+    return run_async(g[0].b, n, first, nullptr, g[0].sum, nullptr);
+  }
+  cpr_batch* b0 = g[0].b;
+  // every member's re-run registration before the kernel. A flush in the middle would drop
+  // the registrations made so far, so where the launch table or the overflow-flag chunks
+  // may not hold the whole group, the flush comes first, before the group's kernel on the
+  // stream, and the group registers into the emptied table
+  const int kind = c->fuse_kind;
+  FusePoint pts[kFuseMax > kFuseMaxArr ? kFuseMax : kFuseMaxArr];
+  int64_t* redo = nullptr;
+  uint32_t* redo_n = nullptr;
+  if (b0->has_rerun) {
+    if (!rerun_room(c, n, na)) {
+      if (const int rc = flush_reruns(c)) return rc;
+    }
+    for (int i = 0; i < na; ++i) {
+      cpr_batch* b = g[i].b;
+      NakParams NP;
+      const bool hyb = rerun_hybrid(b, false, &NP);
+      if (const int rc = register_rerun(b, b->NEP, b->nak_bytes, first, nullptr, nullptr,
+                                        g[i].sum, n, &redo, &redo_n, &pts[i].launch_id,
+                                        &pts[i].ovf, hyb ? &NP : nullptr))
+        return rc;
+    }
+    if (pts[na - 1].launch_id != pts[0].launch_id + (uint32_t)(na - 1))
+      return fail(CPR_E_HIP, "re-run table flushed while a group registered");
+  }
+  // deferred races: one list region per member in one of the context's two list buffers
+  // (run_async), read by the members' eager second passes on the side stream
+  const size_t list_bytes =
+      kind == 2 ? align256((size_t)run_episodes_list_bytes(b0->P, b0->cfg.mode, false, n)) : 0;
+  const int li = c->list_i;
+  if (kind == 2) {
+    if (c->list_pending[li]) {
+      if (c->lists[li].bytes < list_bytes * na) HIP_TRY(hipEventSynchronize(c->list_ev[li]));
+      HIP_TRY(hipStreamWaitEvent(c->stream, c->list_ev[li], 0));
+      c->list_pending[li] = false;
+    }
+    HIP_TRY(c->lists[li].ensure(list_bytes * na));
+  }
+  for (int i = 0; i < na; ++i) {
+    pts[i].t_att = g[i].b->P.t_att;
+    pts[i].sum = g[i].sum;
+    pts[i].list = kind == 2 ? (int64_t*)((uint8_t*)c->lists[li].p + list_bytes * i) : nullptr;
+    if (!b0->has_rerun) {
+      pts[i].ovf = nullptr;
+      pts[i].launch_id = 0;
+    }
+  }
+  const int bpc = run_episodes_fused_blocks_per_cu(b0->P, na);
+  const int64_t lanes = episode_lanes(b0, n, bpc);
+  auto ft = std::make_shared<FuseTime>();
+  ft->size = na;
+  HIP_TRY(hipEventCreate(&ft->ev0));
+  HIP_TRY(hipEventCreate(&ft->ev1));
+  NakParams P = b0->P;
+  const char* wq = getenv("CPR_NAK_WQ");
+  if (!(wq && wq[0] == '0')) HIP_TRY(ctx_next(c, &P.next));
+  HIP_TRY(hipEventRecord(ft->ev0, c->stream));
+  HIP_TRY(launch_run_episodes_fused(P, b0->cfg.seed, first, n, pts, na, lanes, redo, redo_n,
+                                    c->rq_cap, c->stream));
+  // the group's time is its kernel's, on the stream. The second passes below are not in it:
+  // on the side stream they share the device with the next launch and mostly wait for its
+  // workgroups to leave, so a span that ended behind them would hold that launch as well
+  HIP_TRY(hipEventRecord(ft->ev1, c->stream));
+  if (kind == 2) {
+    // every member's eager second pass, an unfused launch with the member's own alpha, on
+    // the side stream behind the group's kernel: they overlap the next launch on the stream
+    const int64_t lanes2 =
+        episode_lanes(b0, n, run_episodes_blocks_per_cu(b0->P, b0->cfg.mode, false));
+    HIP_TRY(hipEventRecord(c->main_ev, c->stream));
+    HIP_TRY(hipStreamWaitEvent(c->side, c->main_ev, 0));
+    for (int i = 0; i < na; ++i)
+      HIP_TRY(launch_run_episodes_second(g[i].b->P, b0->cfg.seed, first, n, pts[i].list, lanes2,
+                                         g[i].sum, redo, redo_n, pts[i].launch_id, c->rq_cap,
+                                         pts[i].ovf, c->side));
+    HIP_TRY(hipEventRecord(c->list_ev[li], c->side));
+    c->list_pending[li] = true;
+    c->list_i ^= 1;
+  }
+  for (int i = 0; i < na; ++i) {
+    cpr_batch* b = g[i].b;
+    b->last_lanes = lanes;
+    b->last_resident = (int64_t)c->cus * bpc * 256;
+    b->fuse_time = ft;
+    b->async_launch = true;
+  }
+  return CPR_OK;
+}
+
 int cpr_run_episodes_async(cpr_batch* b, int64_t n, uint64_t first, cpr_summary* sum_dev,
                            cpr_episode_record* rec_dev) {
   if (!b || !sum_dev) return fail(CPR_E_INVALID_ARG, "NULL argument");
   if (n <= 0) return CPR_OK;
-  HIP_TRY(hipSetDevice(b->ctx->device));
+  cpr_ctx* c = b->ctx;
+  const int kind = fuse_kind(b, rec_dev);
+  const int cap = fuse_cap(kind);
+  const bool fusable = kind != 0 && cap >= 2;
+  // the pending group is launched before any call that does not join it is handled
+  if (!c->fuse.empty() && !(fusable && n == c->fuse_n && first == c->fuse_first &&
+                            fuse_same_launch(c->fuse[0].b, b)))
+    CPR_ENTER(c);
+  if (fusable) {
+    c->fuse.push_back({b, sum_dev});
+    c->fuse_kind = kind;
+    c->fuse_n = n;
+    c->fuse_first = first;
+    if ((int)c->fuse.size() >= cap) CPR_ENTER(c);
+    return CPR_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
   b->async_launch = true;
   return run_async(b, n, first, nullptr, sum_dev, rec_dev);
 }
@@ -1465,6 +1708,7 @@ static int run_sync(cpr_batch* b, int64_t n, uint64_t first, const TraceSource* 
 int cpr_run_episodes(cpr_batch* b, int64_t n, uint64_t first, cpr_summary* summary,
                      cpr_episode_record* records, int records_on_device) {
   if (!b || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (n <= 0) return CPR_OK;
   HIP_TRY(hipSetDevice(b->ctx->device));
   return run_sync(b, n, first, nullptr, summary, records, records_on_device);
@@ -1558,6 +1802,7 @@ static int upload_trace(cpr_batch* b, const cpr_trace* t, TraceSource* out) {
 int cpr_replay(cpr_batch* b, const cpr_trace* t, cpr_summary* summary,
                cpr_episode_record* records, int records_on_device) {
   if (!b || !t || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (b->cfg.network == CPR_NET_ABSTRACT_GAMMA)
     return fail(CPR_E_UNSUPPORTED, "the abstract-gamma mode has no trace replay");
   if (t->n_episodes <= 0) return CPR_OK;
@@ -1584,6 +1829,7 @@ int cpr_node_outputs(cpr_batch* b, int64_t n, uint64_t first, const cpr_trace* t
                      int32_t n_nodes, cpr_episode_record* records, int64_t* node_activations,
                      double* node_rewards) {
   if (!b || !node_activations || !node_rewards) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (b->cfg.protocol == CPR_PROTO_FC16)
     return fail(CPR_E_UNSUPPORTED, "FC16 episodes have no network nodes");
   if (b->cfg.network == CPR_NET_ABSTRACT_GAMMA)
@@ -1892,6 +2138,7 @@ static int launch_lock_reset(cpr_batch* b, const uint8_t* dmask, const uint64_t*
 
 int cpr_reset(cpr_batch* b, const uint8_t* mask, const uint64_t* eps, double* obs) {
   if (!b || !obs) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (b->cfg.protocol == CPR_PROTO_FC16)
     return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
   HIP_TRY(hipSetDevice(b->ctx->device));
@@ -1925,6 +2172,7 @@ int cpr_reset(cpr_batch* b, const uint8_t* mask, const uint64_t* eps, double* ob
 int cpr_step(cpr_batch* b, const int32_t* actions, double* obs, double* reward, uint8_t* done,
              cpr_step_info* info) {
   if (!b || !actions || !obs || !reward || !done) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (!b->reset_done) return fail(CPR_E_STATE, "step before reset");
   const int64_t n = b->cfg.n_lanes;
   const int n_act = b->is_eth ? 24 : b->is_ev ? 8 : 4;
@@ -1960,6 +2208,7 @@ int cpr_step(cpr_batch* b, const int32_t* actions, double* obs, double* reward, 
 
 int cpr_observe_fields(cpr_batch* b, int32_t* fields) {
   if (!b || !fields) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (!b->reset_done) return fail(CPR_E_STATE, "observe before reset");
   const int64_t n = b->cfg.n_lanes;
   HIP_TRY(hipSetDevice(b->ctx->device));
@@ -1988,6 +2237,7 @@ int cpr_observe_fields(cpr_batch* b, int32_t* fields) {
 int cpr_policy_actions(cpr_batch* b, int32_t policy, const double* obs, int64_t n,
                        int32_t* actions) {
   if (!b || !obs || !actions) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (b->cfg.protocol == CPR_PROTO_TAILSTORM) {
     if (policy < 0 || policy > CPR_TS_POLICY_TABLE)
       return fail(CPR_E_INVALID_ARG, "unknown policy");
@@ -2072,6 +2322,7 @@ int cpr_policy_actions(cpr_batch* b, int32_t policy, const double* obs, int64_t 
 int cpr_observation_spec(cpr_batch* b, int32_t* obs_len, int32_t* n_actions, double* low,
                          double* high) {
   if (!b) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   const double inf = __builtin_inf();
   if (b->cfg.protocol == CPR_PROTO_FC16) {
     // fc16.rs:61-73: (a, h, fork index) each mapped x -> x / (1 + x); at most 4 actions
@@ -2253,6 +2504,7 @@ static int nak_rollout_rounds(cpr_batch* b, int64_t n_steps, double* obs, double
 int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint8_t* done,
                 int outputs_on_device, cpr_summary* summary) {
   if (!b || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (b->env_table)
     return fail(CPR_E_UNSUPPORTED, "cpr_rollout (built-in policies) runs every lane at cfg.alpha; "
                                    "this batch has an alpha table (cpr_lane_env_set)");
@@ -2368,6 +2620,7 @@ int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint
 
 int cpr_policy_net_set(cpr_batch* b, const cpr_policy_net* net) {
   if (!b || !net) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (b->cfg.protocol == CPR_PROTO_FC16)
     return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
   if (b->cfg.n_lanes <= 0 || b->cfg.mode != CPR_MODE_GYM)
@@ -2466,6 +2719,7 @@ int cpr_policy_net_forward(cpr_batch* b, const double* obs, int64_t n, int deter
                            uint64_t episode0, int32_t* actions, double* logp, double* value,
                            float* logits) {
   if (!b || !obs) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
   if (n < 1) return fail(CPR_E_INVALID_ARG, "policy net forward: n must be >= 1");
   HIP_TRY(hipSetDevice(b->ctx->device));
@@ -2527,6 +2781,7 @@ static int launch_lane_cursor(cpr_batch* b, const LaneCursor& c) {
 
 int cpr_lane_env_set(cpr_batch* b, const cpr_lane_env* env) {
   if (!b || !env) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (b->cfg.protocol == CPR_PROTO_FC16)
     return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
   if (b->cfg.n_lanes <= 0 || b->cfg.mode != CPR_MODE_GYM)
@@ -2584,6 +2839,7 @@ int cpr_lane_env_set(cpr_batch* b, const cpr_lane_env* env) {
 
 int cpr_lane_alpha(cpr_batch* b, double* alpha) {
   if (!b || !alpha) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   const int64_t n = b->cfg.n_lanes;
   if (!b->has_env) {
     for (int64_t i = 0; i < n; i++) alpha[i] = b->cfg.alpha;
@@ -2606,6 +2862,7 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
                         const cpr_rollout_net_out* out, const cpr_rollout_env_out* env_out,
                         int outputs_on_device, cpr_summary* summary) {
   if (!b || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (b->cfg.protocol == CPR_PROTO_FC16)
     return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
   if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
@@ -2791,6 +3048,7 @@ int cpr_gae(cpr_batch* b, int64_t n_steps, const double* reward, const uint8_t* 
             int on_device) {
   if (!b || !reward || !done || !value || !adv_out || !ret_out)
     return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   const int64_t n = b->cfg.n_lanes;
   if (n <= 0) return fail(CPR_E_UNSUPPORTED, "gae needs lockstep lanes (cfg.n_lanes > 0)");
   if (n_steps < 1) return fail(CPR_E_INVALID_ARG, "gae: n_steps must be >= 1");
@@ -3087,6 +3345,7 @@ static void ppo_stats_out(const double* s, double div, int64_t count, cpr_ppo_st
 
 int cpr_ppo_param_count(cpr_batch* b, int64_t* count) {
   if (!b || !count) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
   int64_t c = 0;
   for (int64_t k : b->pn_cnt) c += k;
@@ -3099,6 +3358,7 @@ int cpr_ppo_gradients(cpr_batch* b, const cpr_ppo_data* data, const int32_t* row
                       cpr_ppo_stats* stats_out) {
   int rc = ppo_check(b, opts);
   if (rc) return rc;
+  CPR_ENTER(b->ctx);
   if (!rows_idx || !grad_out) return fail(CPR_E_INVALID_ARG, "NULL argument");
   if (n_rows < 1 || n_rows > INT32_MAX)
     return fail(CPR_E_INVALID_ARG, "ppo: n_rows must be in 1 .. 2^31 - 1");
@@ -3157,6 +3417,7 @@ int cpr_ppo_update(cpr_batch* b, const cpr_ppo_data* data, const cpr_ppo_opts* o
                    const int32_t* perm, cpr_ppo_stats* stats_out) {
   int rc = ppo_check(b, opts);
   if (rc) return rc;
+  CPR_ENTER(b->ctx);
   PpoDev D;
   rc = ppo_stage(b, data, &D);
   if (rc) return rc;
@@ -3224,6 +3485,7 @@ int cpr_ppo_iterate(cpr_batch* b, int64_t n_steps, const cpr_ppo_opts* opts,
                     cpr_summary* summary, cpr_ppo_stats* stats_out) {
   int rc = ppo_check(b, opts);
   if (rc) return rc;
+  CPR_ENTER(b->ctx);
   if (!summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
   if (n_steps < 1) return fail(CPR_E_INVALID_ARG, "ppo: n_steps must be >= 1");
   const int64_t n = b->cfg.n_lanes;
@@ -3272,6 +3534,7 @@ int cpr_ppo_iterate(cpr_batch* b, int64_t n_steps, const cpr_ppo_opts* opts,
 
 int cpr_policy_net_get(cpr_batch* b, cpr_policy_net* net) {
   if (!b || !net) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
   if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
   const PolNet& N = b->pn;
   std::vector<float*> dst;
@@ -3302,6 +3565,7 @@ int cpr_policy_net_get(cpr_batch* b, cpr_policy_net* net) {
 int cpr_stream_fill(cpr_ctx* ctx, uint64_t seed, uint64_t ep, uint32_t idx0, uint32_t tag,
                     int64_t n, uint32_t* out, double* exp_out) {
   if (!ctx || !out) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(ctx);
   if (n <= 0) return CPR_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   DevBuf o, e;

@@ -8,6 +8,7 @@
 #include "bk_lane.h"
 #include "ethereum_lane.h"
 #include "nakamoto_lane.h"
+#include "nak_fused.h"
 #include "fc16_lane.h"
 #include "summary.h"
 #include "ts_lane.h"
@@ -99,6 +100,41 @@ hipError_t launch_run_episodes(const NakParams& P, uint64_t seed, uint64_t first
                                uint32_t* redo_n, uint32_t launch_id, int64_t redo_cap,
                                uint8_t* ovf, hipStream_t st, const SidePass* side = nullptr);
 int64_t run_episodes_list_bytes(const NakParams& P, int32_t mode, bool recs, int64_t n_eps);
+// Sweep points that share their draws in one lane (kernels_nak_fused.hip, nak_fused.h).
+// fusable: launch_run_episodes would run one of the two timed d = 2 summary kernels with a
+// built-in policy, the instantiations the fused kernel stands for: 1 = the gamma = 0 lazy-clock
+// kernel, 2 = the deferred-race lazy-clock kernel (P.arrive; with its second-pass lists),
+// 0 = neither
+int run_episodes_fusable(const NakParams& P, int32_t mode, bool recs);
+// points per lane: instantiations for 2 .. this (kind 1, kind 2)
+constexpr int kFuseMax = CPR_NAK_FUSE_MAX, kFuseMaxArr = CPR_NAK_FUSE_MAX_ARR;
+// what one point of a fused launch brings of its own (redo entries carry its launch_id; ovf:
+// its overflow flags; both unused when the launch has no redo queue; list: kind 2, its
+// second-pass list of run_episodes_list_bytes)
+struct FusePoint {
+  uint64_t t_att;
+  cpr_summary* sum;
+  uint8_t* ovf;
+  int64_t* list;
+  uint32_t launch_id;
+};
+// na in 2 .. kFuseMax points of P (P.t_att is not read), each over episodes first .. first +
+// n_eps - 1; P.next as in launch_run_episodes. Kind 2: the caller then runs every point's
+// eager second pass (launch_run_episodes_second) behind this kernel
+hipError_t launch_run_episodes_fused(const NakParams& P, uint64_t seed, uint64_t first,
+                                     int64_t n_eps, const FusePoint* pts, int na, int64_t lanes,
+                                     int64_t* redo, uint32_t* redo_n, int64_t redo_cap,
+                                     hipStream_t st);
+// the eager second pass over one list (the deferred-race launch's second kernel, static grid
+// stride over the listed episodes; launch_run_episodes runs its own through this). On a
+// stream other than the main kernel's it gets neither spill nor tie-replay scratch
+hipError_t launch_run_episodes_second(const NakParams& P, uint64_t seed, uint64_t first,
+                                      int64_t n_eps, int64_t* list, int64_t lanes,
+                                      cpr_summary* sum, int64_t* redo, uint32_t* redo_n,
+                                      uint32_t launch_id, int64_t redo_cap, uint8_t* ovf,
+                                      hipStream_t st, double* spill = nullptr,
+                                      uint8_t* replay = nullptr);
+int run_episodes_fused_blocks_per_cu(const NakParams& P, int na);
 // the same fused kernel drawing from a device copy of a cpr_trace (cpr_replay)
 hipError_t launch_replay_episodes(const NakParams& P, const TraceSource& src, int64_t n_eps,
                                   int32_t mode, int64_t activations, double* spill,

@@ -95,23 +95,7 @@ __device__ inline CPR_AI BRef run_loop(NakLane& L, const NakParams& P, const St&
   return L.head(P, M);
 }
 
-// The episode after e (k_run_episodes): with a work-queue counter, the wave's live lanes
-// take the next 64 episodes together (one atomic by the lowest live lane, broadcast), so a
-// wave that runs ahead takes more episodes and a launch ends within about one episode of
-// its slowest wave instead of after a fixed share per wave; the lanes of a wave keep
-// consecutive episodes started together, so their activation counts stay equal (the keyed
-// counter and the deferred races' wave list rely on it). Without: the static grid stride
-__device__ inline CPR_AI int64_t nak_next_episode(unsigned long long* next, int64_t e,
-                                                  int64_t nthreads) {
-  if (next == nullptr) return e + nthreads;
-  const uint64_t live = __ballot(1);
-  const int32_t leader = __builtin_ctzll(live);
-  const int32_t lane = (int32_t)(threadIdx.x % WAVE);
-  unsigned long long base = 0ull;
-  if (lane == leader) base = atomicAdd(next, (unsigned long long)WAVE);
-  base = __shfl(base, leader);
-  return nthreads + (int64_t)base + lane;
-}
+// nak_next_episode (the work queue): summary.h
 
 // POL: nakamoto_ssz policy fixed at compile time (P_HONEST .. P_SM1; these kernels never
 // run the abstract-gamma mode), or -1 for P.policy (and P.abstract_g)
@@ -495,6 +479,13 @@ static RunFn gym_run_fn(const NakParams& P, bool recs, bool defer, ListFn* secon
     return k_run_episodes<CPR_MODE_GYM, SeedSource, POL, 0, 1, 2, 2>;
   return k_run_episodes<CPR_MODE_GYM, SeedSource, POL, 0, 1, 2>;
 }
+int run_episodes_fusable(const NakParams& P, int32_t mode, bool recs) {
+  if (mode != CPR_MODE_GYM || P.abstract_g || P.policy < P_HONEST || P.policy > P_SM1 || recs ||
+      P.d != 2 || !lazy_clock_ok(P) || !CPR_LAZY_CLOCK)
+    return 0;
+  if (!P.arrive) return 1;
+  return deferred_races_ok(P) ? 2 : 0;
+}
 // second: set to the eager second pass when the launch defers its races (else untouched)
 static RunFn run_fn(const NakParams& P, int32_t mode, bool recs, bool defer = false,
                     ListFn* second = nullptr) {
@@ -532,13 +523,6 @@ hipError_t launch_run_episodes(const NakParams& P0, uint64_t seed, uint64_t firs
   hipLaunchKernelGGL(fn, dim3(blocks), dim3(kBlock), 0, st, P, src, n_eps, activations, spill,
                      replay, recs, sum, redo, redo_n, launch_id, redo_cap, list, ovf);
   if (second) {
-    // a few episodes in a hundred (~1 % eager, ~3.5 % with the lazy clock, whose races
-    // near a tie cannot be decided without the clock): the whole grid runs them in one round
-    // (more take more rounds of the same grid-stride loop); blocks without an episode exit
-    // at once
-    const ListSource ls{src, reinterpret_cast<const uint32_t*>(list), list + 1};
-    const unsigned b2 = blocks;
-    P.next = nullptr;  // the second pass: the static grid stride over the listed episodes
     hipStream_t s2 = st;
     if (side) {
       // on the side stream, behind this launch's main kernel: it overlaps the next launch
@@ -552,14 +536,38 @@ hipError_t launch_run_episodes(const NakParams& P0, uint64_t seed, uint64_t firs
       spill = nullptr;
       replay = nullptr;
     }
-    hipLaunchKernelGGL(second, dim3(b2), dim3(kBlock), 0, s2, P, ls, n_eps, activations, spill,
-                       replay, recs, sum, redo, redo_n, launch_id, redo_cap, list, ovf);
+    const hipError_t e2 = launch_run_episodes_second(P0, seed, first, n_eps, list, lanes, sum,
+                                                     redo, redo_n, launch_id, redo_cap, ovf, s2,
+                                                     spill, replay);
+    if (e2 != hipSuccess) return e2;
     if (side) {
       const hipError_t e = hipEventRecord(side->done, s2);
       if (e != hipSuccess) return e;
       *side->ran = true;
     }
   }
+  return hipGetLastError();
+}
+
+// a few episodes in a hundred (~1 % eager, ~3.5 % with the lazy clock, whose races near a tie
+// cannot be decided without the clock): the whole grid runs them in one round (more take more
+// rounds of the same grid-stride loop); blocks without an episode exit at once
+hipError_t launch_run_episodes_second(const NakParams& P0, uint64_t seed, uint64_t first,
+                                      int64_t n_eps, int64_t* list, int64_t lanes,
+                                      cpr_summary* sum, int64_t* redo, uint32_t* redo_n,
+                                      uint32_t launch_id, int64_t redo_cap, uint8_t* ovf,
+                                      hipStream_t st, double* spill, uint8_t* replay) {
+  ListFn second = nullptr;
+  (void)run_fn(P0, CPR_MODE_GYM, false, true, &second);
+  if (!second) return hipErrorInvalidValue;
+  NakParams P = P0;
+  P.u_lazy = lazy_clock_ok(P0) ? lazy_threshold(P0) : 0ull;
+  P.next = nullptr;  // the static grid stride over the listed episodes
+  const SeedSource src{seed, first};
+  const ListSource ls{src, reinterpret_cast<const uint32_t*>(list), list + 1};
+  hipLaunchKernelGGL(second, dim3((unsigned)(lanes / kBlock)), dim3(kBlock), 0, st, P, ls, n_eps,
+                     (int64_t)0, spill, replay, (cpr_episode_record*)nullptr, sum, redo, redo_n,
+                     launch_id, redo_cap, list, ovf);
   return hipGetLastError();
 }
 

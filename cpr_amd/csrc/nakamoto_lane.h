@@ -669,12 +669,18 @@ struct NakLane {
     activate<St, LZ>(P, S, M, draw<St, LZ>(P, S));
   }
 
-  template <class St, int LZ = 0>
+  // CHK = false (LZ only): the caller has made the lazy clock's skip test and exact check
+  // itself (nak_fused.h: once for the lanes that share the activation's draws)
+  template <class St, int LZ = 0, bool CHK = true>
   __host__ __device__ inline CPR_AI void activate(const NakParams& P, const St& S, const LaneMem& M,
                                                   const Draw dr) {
+    static_assert(CHK || LZ != 0, "only the lazy clock is checked by the caller");
     const int32_t miner = dr.miner;
     const double tn = t + dr.dt;
-    if constexpr (LZ) {
+    if constexpr (LZ && !CHK) {
+      // (the clock is neither drawn nor summed: see lazy_overlap_check; LZ = 2: the caller
+      // keeps esum as well)
+    } else if constexpr (LZ) {
       // the uniform's high word (w2 >> 5) against the threshold's: uh >= lazy_hi, or uh == 0
       // (unsigned wrap; U == 0 is among these), or a +inf clock: the exact check. It is
       // exact whenever it runs, so entering it for a few uniforms below u_lazy (those that
@@ -943,9 +949,13 @@ __host__ __device__ inline CPR_AI void races_publish(const St& S, const LaneMem&
 // release strictly first, as the eager check would find. Anything closer (~ulp(t) / delta,
 // 1e-4 of races at the gym's delay; or a +inf clock) cannot be decided without t and flags
 // the episode for the eager second pass, which decides it with t as the eager kernel does.
-template <class St, int LZ = 0>
+// NP > 1 (LZ = 2, nak_fused.h): the list holds the races of NP sweep points per lane; an
+// entry's y is then the +inf flag (bit 0) and its point (bits 1..), and a lane's flag word
+// holds two bits per point
+template <class St, int LZ = 0, int NP = 1>
 __host__ __device__ inline CPR_AI void races_check(const NakLane& L, const NakParams& P,
                                                   const St& S, const LaneMem& M) {
+  static_assert(NP == 1 || LZ == 2, "several points per lane: lazy clock only");
   // the entries are spread over the lanes that are here: in the last grid-stride round of
   // a launch some lanes of the wave have left the episode loop, and an entry assigned to
   // one of them would never be checked. (On the host a wave is emulated phase by phase
@@ -973,7 +983,9 @@ __host__ __device__ inline CPR_AI void races_check(const NakLane& L, const NakPa
       const double T = (double)e.x * (P.ev * (1.0 / 4096.0)) * (1.0 + 1e-9) + P.delta;
       const int32_t ex = (int32_t)((bitsd(T) >> 52) & 0x7ffu);  // T > 0, normal
       const double ulp = dbits((uint64_t)(ex > 52 ? ex - 52 : 1) << 52);
-      if (e.y != 0u || !(a < P.delta - ulp)) flag_or(&M.rflag[owner], 2);
+      const uint32_t inf = NP > 1 ? (e.y & 1u) : e.y;
+      const int32_t redo = NP > 1 ? 2 << (2 * (e.y >> 1)) : 2;
+      if (inf != 0u || !(a < P.delta - ulp)) flag_or(&M.rflag[owner], redo);
       continue;
     }
     const double t = dbits((uint64_t)e.x | ((uint64_t)e.y << 32));

@@ -8,6 +8,7 @@
 
 #include "../../include/cpr_hip.h"
 #include "cpr_stream.h"
+#include "nakamoto_lane.h"
 
 #pragma clang fp contract(off)
 
@@ -198,5 +199,23 @@ struct TraceSource {
   }
 };
 
+// The episode after e (k_run_episodes, k_run_episodes_fused): with a work-queue counter, the
+// wave's live lanes take the next WAVE episodes together (one atomic by the lowest live lane,
+// broadcast), so a wave that runs ahead takes more episodes and a launch ends within about
+// one episode of its slowest wave instead of after a fixed share per wave; the lanes of a
+// wave keep consecutive episodes started together, so their activation counts stay equal
+// (the keyed counter and the deferred races' wave list rely on it). Without: the static
+// grid stride
+__device__ inline __attribute__((always_inline)) int64_t nak_next_episode(
+    unsigned long long* next, int64_t e, int64_t nthreads) {
+  if (next == nullptr) return e + nthreads;
+  const uint64_t live = __ballot(1);
+  const int32_t leader = __builtin_ctzll(live);
+  const int32_t lane = (int32_t)(threadIdx.x % WAVE);
+  unsigned long long base = 0ull;
+  if (lane == leader) base = atomicAdd(next, (unsigned long long)WAVE);
+  base = __shfl(base, leader);
+  return nthreads + (int64_t)base + lane;
+}
 
 }  // namespace cpr

@@ -52,6 +52,8 @@ class Context:
         return e.value, f.value, ms.value
 
     def synchronize(self):
+        """Launches what ``Batch.run_async`` deferred, runs the exact re-runs of flagged
+        episodes and waits: summaries and records are complete afterwards."""
         L.check(L.lib().cpr_synchronize(self.handle))
 
     def stream_fill(self, seed, episode, idx0, tag, n, with_exp=False):
@@ -381,7 +383,9 @@ class Batch:
         return rec, acts, rews
 
     def last_launch(self):
-        """(kernel_ms, activations) of the last fused-episode launch (HIP events)."""
+        """(kernel_ms, activations) of the last fused-episode launch (HIP events). After
+        ``run_async`` it waits for that launch; a point that ran in a group of m sweep points
+        reports the group's kernel time / m."""
         ms = ctypes.c_double()
         acts = ctypes.c_int64()
         L.check(L.lib().cpr_last_launch(self.handle, ctypes.byref(ms), ctypes.byref(acts)))
@@ -395,6 +399,13 @@ class Batch:
         return lanes.value, res.value
 
     def run_async(self, n_episodes, first_episode, summary_dev_ptr, records_dev_ptr=None):
+        """cpr_run_episodes_async: the summary (a zeroed device cpr_summary) is complete after
+        ``ctx.synchronize()``. The launch may be deferred until then: summary-only calls of
+        one context on the gym's two-defender networks (gamma <= .5) that share seed, first
+        episode and episode count (an alpha sweep with common random numbers) run as one
+        kernel per group of up to five (gamma = 0) or two, with the same results; any other call
+        on the context or its batches launches what is pending first. ``CPR_NAK_FUSE`` (read
+        at every call) is the largest group; 0 launches every call at once."""
         L.check(
             L.lib().cpr_run_episodes_async(
                 self.handle, n_episodes, first_episode, summary_dev_ptr, records_dev_ptr

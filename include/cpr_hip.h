@@ -372,7 +372,18 @@ int cpr_run_episodes(cpr_batch* b, int64_t n_episodes, uint64_t first_episode,
  * forced inside this call when the context's re-run table or overflow-flag chunks are full)
  * waits for the stream to read how many episodes were queued, so that it can size the
  * re-run grid; an _async call that forces one therefore returns only after the launches
- * before it have finished. */
+ * before it have finished.
+ * The launch itself may be deferred until then. Nakamoto summary-only calls (no records)
+ * on the gym's selfish-mining network with two defenders (gamma = 0, or 0 < gamma <= .5), a
+ * built-in policy and only max_steps <= 2^14 ending the episode wait in the context's pending
+ * group; calls that share seed, first_episode, n_episodes and every parameter but alpha (a
+ * sweep with common random numbers) join it and run as one kernel that computes each
+ * activation's draws once for all of them (up to five points at gamma = 0, two otherwise);
+ * the summaries are the same words as those of separate launches. The group is
+ * launched when it is full, before a call that does not join it is handled, and at the
+ * start of every other entry point that takes the context or one of its batches. An error of
+ * a deferred launch is returned by the call that triggers the launch. CPR_NAK_FUSE (read at
+ * every call) gives the largest group; 0 or 1: every call launches at once. */
 int cpr_run_episodes_async(cpr_batch* b, int64_t n_episodes, uint64_t first_episode,
                            cpr_summary* summary_dev, cpr_episode_record* records_dev);
 int cpr_synchronize(cpr_ctx* ctx);
@@ -400,7 +411,12 @@ int cpr_node_outputs(cpr_batch* b, int64_t n_episodes, uint64_t first_episode,
                      int64_t* node_activations, double* node_rewards);
 /* device time (HIP events on the context's stream) of the last episode-kernel launch of
  * this batch, and the activations it simulated (valid after cpr_run_episodes returns;
- * after cpr_run_episodes_async + cpr_synchronize the time is valid and activations is -1) */
+ * after cpr_run_episodes_async the call launches a deferred launch, waits for the end of
+ * the launch's kernel (also where the call was not deferred; the caller need not have
+ * synchronized) and activations is -1; for a call that ran in a group of m the time is the
+ * group's kernel time / m, so that the times of a sweep's points add up to the time of its
+ * kernels on the context's stream. The eager second passes of a group with deferred races
+ * run beside the next launch on the side stream and are not in that time) */
 int cpr_last_launch(cpr_batch* b, double* kernel_ms, int64_t* activations);
 /* shape of the last episode-kernel launch of this batch (fused episodes, replay, rollout):
  * lanes = device lanes launched; resident = lanes the device holds at once for that kernel

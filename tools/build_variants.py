@@ -56,7 +56,8 @@ def main():
         print("built", out / f"{tag}{w}.so")
 
 
-ALL = ["kernels.hip", *EV, "kernels_fc16.hip"]
+ALL = ["kernels.hip", "kernels_nak_fused.hip", "kernels_nak_rollout.hip", *EV, "kernels_fc16.hip",
+       "kernels_policy.hip", "kernels_ppo.hip"]
 
 
 def build_def(objdir, out, flags, tag, tus, defs):

@@ -20,6 +20,7 @@ CPR_E_UNSUPPORTED = -2
 CPR_E_HIP = -3
 CPR_E_CAPACITY = -4
 CPR_E_STATE = -5
+CPR_E_INTERNAL = -6
 
 PROTO_NAKAMOTO = 0
 PROTO_ETHEREUM = 1
@@ -296,6 +297,68 @@ class RolloutEnvOut(ctypes.Structure):
     ]
 
 
+# the assumption schedule (cpr_lane_env_schedule): enum cpr_alpha_schedule
+SCHEDULE_CHOICE = 0
+SCHEDULE_CYCLE = 1
+
+
+class EvalOptsC(ctypes.Structure):
+    """cpr_eval_opts (include/cpr_hip.h)."""
+
+    _fields_ = [
+        ("episodes_per_alpha", ctypes.c_int64),
+        ("first_episode", ctypes.c_uint64),
+        ("deterministic", ctypes.c_int32),
+        ("check_every", ctypes.c_int64),
+    ]
+
+
+class EvalRecord(ctypes.Structure):
+    """cpr_eval_record: one finished episode of an evaluation."""
+
+    _fields_ = [
+        ("episode", ctypes.c_uint64),
+        ("alpha", ctypes.c_double),
+        ("episode_reward", ctypes.c_double),
+        ("episode_sim_time", ctypes.c_double),
+        ("episode_chain_time", ctypes.c_double),
+        ("episode_progress", ctypes.c_double),
+        ("reward_attacker", ctypes.c_double),
+        ("reward_defender", ctypes.c_double),
+        ("episode_n_activations", ctypes.c_int64),
+        ("episode_n_steps", ctypes.c_int64),
+        ("height", ctypes.c_int64),
+        ("alpha_index", ctypes.c_int32),
+        ("status", ctypes.c_uint32),
+    ]
+
+
+_NP = {ctypes.c_uint64: "<u8", ctypes.c_double: "<f8", ctypes.c_int64: "<i8",
+       ctypes.c_int32: "<i4", ctypes.c_uint32: "<u4"}
+EVAL_RECORD_DTYPE = np.dtype([(n, _NP[t]) for n, t in EvalRecord._fields_])
+assert EVAL_RECORD_DTYPE.itemsize == ctypes.sizeof(EvalRecord)
+
+# enum cpr_eval_column: the columns EvalCallback logs, in cpr_eval_alpha's order
+EVAL_COLUMNS = ("episode_reward", "episode_sim_time", "episode_chain_time", "episode_progress",
+                "episode_n_activations")
+
+
+class EvalAlpha(ctypes.Structure):
+    """cpr_eval_alpha: one alpha's statistics over its valid episodes."""
+
+    _fields_ = [
+        ("alpha", ctypes.c_double),
+        ("n", ctypes.c_int64),
+        ("mean", ctypes.c_double * len(EVAL_COLUMNS)),
+        ("std", ctypes.c_double * len(EVAL_COLUMNS)),
+    ]
+
+
+EVAL_ALPHA_DTYPE = np.dtype([("alpha", "<f8"), ("n", "<i8"), ("mean", "<f8", (len(EVAL_COLUMNS),)),
+                             ("std", "<f8", (len(EVAL_COLUMNS),))])
+assert EVAL_ALPHA_DTYPE.itemsize == ctypes.sizeof(EvalAlpha)
+
+
 class PpoOptsC(ctypes.Structure):
     """cpr_ppo_opts (include/cpr_hip.h)."""
 
@@ -472,6 +535,9 @@ EXPORTS = [
     "cpr_rollout_net",
     "cpr_lane_env_set",
     "cpr_lane_alpha",
+    "cpr_lane_env_schedule",
+    "cpr_eval_net",
+    "cpr_policy_net_copy",
     "cpr_rollout_net_env",
     "cpr_gae",
     "cpr_ppo_opts_default",
@@ -530,6 +596,9 @@ def _declare(L):
                                   P(Summary)]
     L.cpr_lane_env_set.argtypes = [vp, P(LaneEnvC)]
     L.cpr_lane_alpha.argtypes = [vp, vp]
+    L.cpr_lane_env_schedule.argtypes = [vp, ctypes.c_int]
+    L.cpr_eval_net.argtypes = [vp, P(EvalOptsC), vp, vp, vp, P(Summary)]
+    L.cpr_policy_net_copy.argtypes = [vp, vp]
     L.cpr_rollout_net_env.argtypes = [vp, ctypes.c_int64, ctypes.c_int, P(RolloutNetOut),
                                       P(RolloutEnvOut), ctypes.c_int, P(Summary)]
     L.cpr_gae.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp,

@@ -217,6 +217,12 @@ struct cpr_batch {
   cpr_lane_env env = {};  // n_alpha >= 1 once set (cfg.alpha alone without a table)
   bool env_table = false; // the caller gave a table: cpr_rollout is refused
   DevBuf le_tab_t, le_tab_a, le_lane_t, le_lane_a, le_acc;
+  int32_t schedule = CPR_SCHEDULE_CHOICE;  // cpr_lane_env_schedule
+  // cpr_eval_net: the set's records, per-lane episode reward, the finished-episode counter,
+  // per-alpha summaries and statistics; `parked`: an evaluation left the lanes in arbitrary
+  // later episodes, and stepping them waits for a reset of every lane
+  DevBuf ev_rec, ev_acc, ev_cnt, ev_sum, ev_alpha;
+  bool parked = false;
   // the learner (cpr_ppo_*): where each parameter array stands in pn_w (floats, arrays padded
   // to 4) and its length, in the flat gradient's order; Adam's moments and step count; the
   // number of updates since the network was set (the permutation's counter); per-minibatch
@@ -2109,6 +2115,7 @@ static int launch_lock_reset(cpr_batch* b, const uint8_t* dmask, const uint64_t*
     A.eps = deps;
     A.seed = b->cfg.seed;
     A.n_alpha = b->env.n_alpha;
+    A.schedule = b->schedule;
     A.tab_t = (const uint64_t*)b->le_tab_t.p;
     A.tab_a = (const double*)b->le_tab_a.p;
     A.lane_t = (uint64_t*)b->le_lane_t.p;
@@ -2150,6 +2157,11 @@ int cpr_reset(cpr_batch* b, const uint8_t* mask, const uint64_t* eps, double* ob
     for (int64_t i = 0; i < n; i++)
       if (!mask[i]) return fail(CPR_E_STATE, "first reset must include every lane");
   }
+  if (b->parked && mask) {
+    for (int64_t i = 0; i < n; i++)
+      if (!mask[i])
+        return fail(CPR_E_STATE, "the reset after cpr_eval_net must include every lane");
+  }
   const uint8_t* dmask = nullptr;
   const uint64_t* deps = nullptr;
   if (mask) {
@@ -2166,6 +2178,7 @@ int cpr_reset(cpr_batch* b, const uint8_t* mask, const uint64_t* eps, double* ob
   HIP_TRY(hipMemcpyAsync(obs, b->l_obs.p, (size_t)n * ol * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   b->reset_done = true;
+  b->parked = false;
   return CPR_OK;
 }
 
@@ -2174,6 +2187,7 @@ int cpr_step(cpr_batch* b, const int32_t* actions, double* obs, double* reward, 
   if (!b || !actions || !obs || !reward || !done) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
   if (!b->reset_done) return fail(CPR_E_STATE, "step before reset");
+  if (b->parked) return fail(CPR_E_STATE, "step after cpr_eval_net without a reset");
   const int64_t n = b->cfg.n_lanes;
   const int n_act = b->is_eth ? 24 : b->is_ev ? 8 : 4;
   const int ol = obs_len_of(b->cfg);
@@ -2508,6 +2522,7 @@ int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint
   if (b->env_table)
     return fail(CPR_E_UNSUPPORTED, "cpr_rollout (built-in policies) runs every lane at cfg.alpha; "
                                    "this batch has an alpha table (cpr_lane_env_set)");
+  if (b->parked) return fail(CPR_E_STATE, "rollout after cpr_eval_net without a reset");
   const bool is_nak = !b->is_ev && !b->is_eth;
   if (is_nak) {
     // the closed-form lane's rollout (k_nak_rollout): the gym's networks, policies the lane
@@ -2866,6 +2881,7 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
   if (b->cfg.protocol == CPR_PROTO_FC16)
     return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
   if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
+  if (b->parked) return fail(CPR_E_STATE, "rollout after cpr_eval_net without a reset");
   if (n_steps <= 0) return CPR_OK;
   HIP_TRY(hipSetDevice(b->ctx->device));
   int rc = ensure_lockstep(b);
@@ -3038,6 +3054,270 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
   summary->status_other += s.status_other;
   summary->invalid += s.invalid;
   for (int i = 0; i < CPR_HIST_BINS; i++) summary->hist[i] += s.hist[i];
+  return CPR_OK;
+}
+
+int cpr_lane_env_schedule(cpr_batch* b, int schedule) {
+  if (!b) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
+  if (b->cfg.protocol == CPR_PROTO_FC16)
+    return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
+  if (b->cfg.n_lanes <= 0 || b->cfg.mode != CPR_MODE_GYM)
+    return fail(CPR_E_UNSUPPORTED, "a lane env needs lockstep lanes (CPR_MODE_GYM, "
+                                   "cfg.n_lanes > 0)");
+  if (b->reset_done)
+    return fail(CPR_E_STATE, "cpr_lane_env_schedule after the batch's first reset or rollout");
+  if (schedule != CPR_SCHEDULE_CHOICE && schedule != CPR_SCHEDULE_CYCLE)
+    return fail(CPR_E_INVALID_ARG, "lane env: unknown schedule");
+  b->schedule = schedule;
+  return CPR_OK;
+}
+
+// ---------------------------------------------------------------- evaluation (cpr_eval_net)
+
+static void summary_add(cpr_summary* d, const cpr_summary& s) {
+  d->episodes += s.episodes;
+  d->steps += s.steps;
+  d->activations += s.activations;
+  d->reward_attacker_fx += s.reward_attacker_fx;
+  d->reward_defender_fx += s.reward_defender_fx;
+  d->progress_fx += s.progress_fx;
+  d->rel_revenue_fx += s.rel_revenue_fx;
+  d->rel_revenue_sq_fx += s.rel_revenue_sq_fx;
+  d->orphans += s.orphans;
+  d->status_tie += s.status_tie;
+  d->status_overlap += s.status_overlap;
+  d->status_other += s.status_other;
+  d->invalid += s.invalid;
+  for (int i = 0; i < CPR_HIST_BINS; i++) d->hist[i] += s.hist[i];
+}
+
+int cpr_eval_net(cpr_batch* b, const cpr_eval_opts* opts, cpr_eval_record* records,
+                 cpr_eval_alpha* per_alpha, cpr_summary* per_alpha_summary, cpr_summary* total) {
+  if (!b || !opts || !per_alpha) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
+  if (b->cfg.protocol == CPR_PROTO_FC16)
+    return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
+  if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
+  if (opts->episodes_per_alpha < 1)
+    return fail(CPR_E_INVALID_ARG, "eval: episodes_per_alpha must be >= 1");
+  if (opts->check_every < 0) return fail(CPR_E_INVALID_ARG, "eval: check_every < 0");
+  const int64_t max_steps = b->cfg.max_steps;
+  if (max_steps <= 0)
+    return fail(CPR_E_UNSUPPORTED, "eval: cfg.max_steps <= 0 leaves an episode's length unbounded");
+  const bool env = b->has_env;
+  const int32_t A = env ? b->env.n_alpha : 1;
+  if (A > 1 && b->schedule != CPR_SCHEDULE_CYCLE)
+    return fail(CPR_E_UNSUPPORTED, "eval: a table of several alphas needs CPR_SCHEDULE_CYCLE "
+                                   "(cpr_lane_env_schedule): a keyed choice gives its alphas "
+                                   "unequal shares of the set");
+  if (opts->episodes_per_alpha > (int64_t)((1ull << 40) / (uint64_t)A))
+    return fail(CPR_E_INVALID_ARG, "eval: more than 2^40 episodes");
+  const int64_t epa = opts->episodes_per_alpha, n_set = epa * A;
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  int rc = ensure_lockstep(b);
+  if (rc) return rc;
+  const int64_t n = b->cfg.n_lanes;
+  hipStream_t st = b->ctx->stream;
+  if (!b->ev0) {
+    HIP_TRY(hipEventCreate(&b->ev0));
+    HIP_TRY(hipEventCreate(&b->ev1));
+  }
+  HIP_TRY(b->pn_step.ensure((size_t)n * 8));
+  HIP_TRY(b->ev_rec.ensure((size_t)n_set * sizeof(cpr_eval_record)));
+  HIP_TRY(b->ev_acc.ensure((size_t)n * 8));
+  HIP_TRY(b->ev_cnt.ensure(8));
+  HIP_TRY(b->ev_sum.ensure((size_t)A * sizeof(cpr_summary)));
+  HIP_TRY(b->ev_alpha.ensure((size_t)A * sizeof(cpr_eval_alpha)));
+  {  // SB3's evaluate_policy begins with a reset: lane i to episode first_episode + i
+    std::vector<uint64_t> ids((size_t)n);
+    for (int64_t i = 0; i < n; i++) ids[(size_t)i] = opts->first_episode + (uint64_t)i;
+    HIP_TRY(hipMemcpy(b->l_eps.p, ids.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemsetAsync(b->pn_step.p, 0, (size_t)n * 8, st));
+  HIP_TRY(hipMemsetAsync(b->ev_rec.p, 0, (size_t)n_set * sizeof(cpr_eval_record), st));
+  HIP_TRY(hipMemsetAsync(b->ev_acc.p, 0, (size_t)n * 8, st));
+  HIP_TRY(hipMemsetAsync(b->ev_cnt.p, 0, 8, st));
+  HIP_TRY(hipMemsetAsync(b->ev_sum.p, 0, (size_t)A * sizeof(cpr_summary), st));
+  const StepBuffers sb = step_buffers(b);
+  HIP_TRY(hipEventRecord(b->ev0, st));
+  // from here on the lanes no longer stand where the caller left them
+  b->reset_done = true;
+  b->parked = true;
+  uint64_t* ep = (uint64_t*)b->l_eps.p;
+  rc = launch_lock_reset(b, nullptr, ep, sb.obs);
+  if (rc) return rc;
+  PolIO io = {};
+  io.n = n;
+  io.deterministic = opts->deterministic ? 1 : 0;
+  io.seed = b->cfg.seed;
+  io.ep = ep;
+  io.step = (const int64_t*)b->pn_step.p;
+  io.obs = sb.obs;
+  io.action = (int32_t*)b->l_act.p;
+  io.alpha_col = -1;
+  if (env && b->env.alpha_column >= 0) {
+    io.lane_alpha = (const double*)b->le_lane_a.p;
+    io.alpha_col = b->env.alpha_column;
+  }
+  EvalCollect C = {};
+  C.reward = sb.reward;
+  C.done = sb.done;
+  C.era = sb.era;
+  C.erd = sb.erd;
+  C.eprog = sb.eprog;
+  C.ect = sb.ect;
+  C.est = sb.est;
+  C.esteps = sb.esteps;
+  C.eacts = sb.eacts;
+  C.hh = sb.hh;
+  C.status = sb.status;
+  C.orphans_from_progress = b->is_ev ? 1 : 0;
+  C.ep = ep;
+  C.step = (int64_t*)b->pn_step.p;
+  C.mask = (uint8_t*)b->l_mask.p;
+  C.ep_reward = (double*)b->ev_acc.p;
+  C.cfg_alpha = b->cfg.alpha;
+  C.n_alpha = A;
+  C.schedule = b->schedule;
+  C.seed = b->cfg.seed;
+  if (env) {
+    C.gym_reward = b->env.gym_reward;
+    C.reward_shape = b->env.reward_shape;
+    C.dense_target = b->env.dense_target;
+    C.lane_alpha = (const double*)b->le_lane_a.p;
+    C.dense_acc = (double*)b->le_acc.p;
+  }
+  C.first = opts->first_episode;
+  C.n_set = n_set;
+  C.records = (cpr_eval_record*)b->ev_rec.p;
+  C.finished = (unsigned long long*)b->ev_cnt.p;
+  // every episode ends within max_steps steps and a lane runs at most ceil(n_set / n) episodes
+  // of the set, back to back from the first step: `bound` steps finish the set
+  const int64_t rounds = (n_set + n - 1) / n;
+  if (rounds > INT64_MAX / max_steps) return fail(CPR_E_INVALID_ARG, "eval: step bound overflows");
+  const int64_t bound = rounds * max_steps;
+  const int64_t every = opts->check_every > 0 ? opts->check_every : max_steps;
+  int64_t t = 0;
+  for (;;) {
+    const int64_t chunk = std::min<int64_t>(every, bound - t);
+    for (int64_t k = 0; k < chunk; ++k) {
+      HIP_TRY(launch_policy_forward(b->pn, io, st));
+      rc = launch_lock_step(b, io.action, sb);
+      if (rc) return rc;
+      HIP_TRY(launch_eval_collect(C, n, st));
+      // a finished lane is reset before it is stepped again (its buffers are sized by max_steps)
+      rc = launch_lock_reset(b, C.mask, ep, sb.obs);
+      if (rc) return rc;
+    }
+    t += chunk;
+    unsigned long long fin = 0;
+    HIP_TRY(hipMemcpyAsync(&fin, C.finished, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((int64_t)fin == n_set) break;
+    if (t >= bound)
+      return fail(CPR_E_INTERNAL, "eval: " + std::to_string(fin) + " of " + std::to_string(n_set) +
+                                      " episodes finished after " + std::to_string(bound) +
+                                      " steps");
+  }
+  EvalReduce R = {};
+  R.records = C.records;
+  R.first = opts->first_episode;
+  R.per_alpha = epa;
+  R.n_alpha = A;
+  R.tab_a = env ? (const double*)b->le_tab_a.p : nullptr;
+  R.cfg_alpha = b->cfg.alpha;
+  R.sums = (cpr_summary*)b->ev_sum.p;
+  R.out = (cpr_eval_alpha*)b->ev_alpha.p;
+  HIP_TRY(launch_eval_reduce(R, st));
+  HIP_TRY(hipEventRecord(b->ev1, st));
+  std::vector<cpr_summary> sums((size_t)A);
+  HIP_TRY(hipMemcpyAsync(sums.data(), R.sums, (size_t)A * sizeof(cpr_summary),
+                         hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(per_alpha, R.out, (size_t)A * sizeof(cpr_eval_alpha),
+                         hipMemcpyDeviceToHost, st));
+  if (records)
+    HIP_TRY(hipMemcpyAsync(records, C.records, (size_t)n_set * sizeof(cpr_eval_record),
+                           hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  cpr_summary tot = {};
+  for (int32_t j = 0; j < A; j++) {
+    if (per_alpha_summary) per_alpha_summary[j] = sums[(size_t)j];
+    summary_add(&tot, sums[(size_t)j]);
+  }
+  if (total) *total = tot;
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+  b->last_ms = ms;
+  b->last_acts = tot.activations;
+  b->async_launch = false;
+  b->last_lanes = n;
+  b->last_resident = n;
+  return CPR_OK;
+}
+
+int cpr_policy_net_copy(cpr_batch* dst, cpr_batch* src) {
+  if (!dst || !src) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(dst->ctx);
+  if (dst->ctx != src->ctx)
+    return fail(CPR_E_INVALID_ARG, "policy net copy: the batches belong to different contexts");
+  if (!src->has_net) return fail(CPR_E_STATE, "policy net copy: the source has no network");
+  if (dst == src) return CPR_OK;
+  if (dst->cfg.protocol == CPR_PROTO_FC16)
+    return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
+  if (dst->cfg.n_lanes <= 0 || dst->cfg.mode != CPR_MODE_GYM)
+    return fail(CPR_E_UNSUPPORTED, "a policy network needs lockstep lanes (CPR_MODE_GYM, "
+                                   "cfg.n_lanes > 0)");
+  const PolNet& S = src->pn;
+  int32_t ol = 0, na = 0;
+  int rc = cpr_observation_spec(dst, &ol, &na, nullptr, nullptr);
+  if (rc) return rc;
+  if (ol != S.obs_len || na != S.n_actions)
+    return fail(CPR_E_INVALID_ARG, "policy net copy: observation or action width differs");
+  if (dst->has_net) {
+    const PolNet& D = dst->pn;
+    bool same = D.depth == S.depth && D.width_pi == S.width_pi && D.width_vf == S.width_vf &&
+                D.n_extra == S.n_extra;
+    for (int i = 0; same && i < S.n_extra; i++) same = D.extra[i] == S.extra[i];
+    if (!same)
+      return fail(CPR_E_INVALID_ARG, "policy net copy: depth, widths, n_extra or extras differ");
+  }
+  if (dst->has_env && dst->env.alpha_column >= S.n_extra)
+    return fail(CPR_E_INVALID_ARG, "policy net: n_extra does not reach the lane env's "
+                                   "alpha_column (cpr_lane_env_set)");
+  HIP_TRY(hipSetDevice(dst->ctx->device));
+  const int64_t lds = policy_lds_bytes(S.depth, S.width_pi, S.width_vf);
+  if (lds > policy_lds_limit())
+    return fail(CPR_E_UNSUPPORTED, "policy net: needs " + std::to_string(lds) +
+                                       " B of LDS per workgroup, the device has " +
+                                       std::to_string(policy_lds_limit()));
+  hipStream_t st = dst->ctx->stream;
+  const size_t bytes = (size_t)src->pn_total * sizeof(float);
+  if (bytes > dst->pn_w.bytes) {
+    // growing frees the old buffer: a forward of the previous network may still be reading it
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(dst->pn_w.ensure(bytes));
+  }
+  // stream ordered: behind the source's updates, before the destination's next forward
+  HIP_TRY(hipMemcpyAsync(dst->pn_w.p, src->pn_w.p, bytes, hipMemcpyDeviceToDevice, st));
+  PolNet N = S;
+  const float* sbase = (const float*)src->pn_w.p;
+  const float* dbase = (const float*)dst->pn_w.p;
+  for (PolLayer* Ls : {N.pi, N.vf})
+    for (int l = 0; l <= N.depth; l++) {
+      Ls[l].W = dbase + (Ls[l].W - sbase);
+      Ls[l].b = dbase + (Ls[l].b - sbase);
+    }
+  dst->pn_off = src->pn_off;
+  dst->pn_cnt = src->pn_cnt;
+  dst->pn_total = src->pn_total;
+  dst->ppo_t = 0;
+  dst->ppo_updates = 0;
+  if (dst->pp_m.p) HIP_TRY(hipMemsetAsync(dst->pp_m.p, 0, dst->pp_m.bytes, st));
+  if (dst->pp_v.p) HIP_TRY(hipMemsetAsync(dst->pp_v.p, 0, dst->pp_v.bytes, st));
+  if (!dst->has_net) dst->pp_part.release();
+  dst->pn = N;
+  dst->has_net = true;
   return CPR_OK;
 }
 

@@ -8,11 +8,17 @@
 //   k_lane_assign      the lane env's assumption schedule: threshold and alpha of the masked
 //                      lanes' new episodes, before every lockstep reset
 //   k_policy_tail      activations of the episodes still running when the rollout ends
+//   k_eval_collect     per-step bookkeeping of cpr_eval_net: the episode's reward summed per
+//                      lane, one cpr_eval_record per finished episode of the set at a
+//                      deterministic slot, the finished-episode counter
+//   k_eval_reduce      after the evaluation, one workgroup per alpha: its cpr_summary and the
+//                      mean / std of the logged columns in eval.h's order
 //   k_lock_cursor      where the Nakamoto lockstep lanes stand when a rollout begins
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "eval.h"
 #include "kernels.h"
 #include "lane_env.h"
 #include "nak_rollout.h"
@@ -165,12 +171,121 @@ __global__ __launch_bounds__(kBlock) void k_policy_tail(const int64_t* acts, con
     atomicAdd((unsigned long long*)&sum->activations, (unsigned long long)v);
 }
 
+__global__ __launch_bounds__(kBlock) void k_eval_collect(EvalCollect C, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t fin = 0;
+  if (i < n) {
+    const uint8_t d = C.done[i];
+    double r = C.reward[i];
+    double alpha = C.cfg_alpha;
+    if (C.lane_alpha) {  // the gym's reward wrapper and shape (lane_env.h), as k_policy_collect
+      GymStepInfo s;
+      s.reward = r;
+      s.done = d != 0;
+      s.era = C.era[i];
+      s.erd = C.erd[i];
+      s.progress = C.eprog[i];
+      s.n_activations = C.eacts[i];
+      alpha = C.lane_alpha[i];
+      double acc = C.dense_acc[i];
+      r = gym_reward(C.gym_reward, C.dense_target, s, &acc);
+      if (C.gym_reward == CPR_GYM_REWARD_DENSE_PER_PROGRESS) C.dense_acc[i] = acc;
+      r = shape_reward(C.reward_shape, r, alpha, s);
+    }
+    const double total = C.ep_reward[i] + r;  // erw_episode_reward, in step order from 0
+    C.mask[i] = d;
+    if (d) {
+      const uint64_t e = C.ep[i];
+      const uint64_t slot = e - C.first;
+      if (e >= C.first && slot < (uint64_t)C.n_set) {
+        const double prog = C.eprog[i];
+        cpr_eval_record rec;
+        rec.episode = e;
+        rec.alpha = alpha;
+        rec.episode_reward = total;
+        rec.episode_sim_time = C.est[i];
+        rec.episode_chain_time = C.ect[i];
+        rec.episode_progress = prog;
+        rec.reward_attacker = C.era[i];
+        rec.reward_defender = C.erd[i];
+        rec.episode_n_activations = C.eacts[i];
+        rec.episode_n_steps = C.esteps[i];
+        rec.height = C.orphans_from_progress ? (int64_t)prog : (int64_t)C.hh[i];
+        rec.alpha_index =
+            C.lane_alpha ? lane_alpha_entry(C.schedule, C.seed, e, C.n_alpha) : 0;
+        rec.status = C.status[i];
+        C.records[slot] = rec;
+        fin = 1;
+      }
+      C.ep_reward[i] = 0.0;
+      C.ep[i] = e + (uint64_t)n;  // VecEnv auto-reset: the lane's next episode
+      C.step[i] = 0;
+    } else {
+      C.ep_reward[i] = total;
+      C.step[i] += 1;
+    }
+  }
+  // every lane of the wave takes part in the shuffle: one atomic per wave that finished any
+  fin = wave_sum(fin);
+  if ((threadIdx.x & 63) == 0 && fin) atomicAdd(C.finished, (unsigned long long)fin);
+}
+
+static_assert(kEvalThreads == kBlock, "block_flush reduces a workgroup of kBlock threads");
+
+__global__ __launch_bounds__(kEvalThreads) void k_eval_reduce(EvalReduce R) {
+  __shared__ int32_t hist[CPR_HIST_BINS];
+  __shared__ double p[kEvalThreads];
+  __shared__ unsigned long long n_valid;
+  const int t = (int)threadIdx.x;
+  const int32_t j = (int32_t)blockIdx.x;  // the table entry
+  const uint64_t A = (uint64_t)R.n_alpha;
+  // the first slot s with (first + s) mod A = j; the entry's records follow at stride A
+  const int64_t s0 = (int64_t)(((uint64_t)j + A - R.first % A) % A);
+  const cpr_eval_record* recs = R.records + s0;
+  const int64_t stride = (int64_t)A, count = R.per_alpha;
+  if (t < CPR_HIST_BINS) hist[t] = 0;
+  if (t == 0) n_valid = 0ull;
+  __syncthreads();
+  Acc acc = {};
+  for (int64_t k = t; k < count; k += kEvalThreads) {
+    const EvalTerms T = eval_terms(recs[k * stride]);
+    acc_episode(acc, T.ra_fx, T.rd_fx, T.prog_fx, T.rel, T.height, T.steps, T.acts, T.status,
+                hist);
+  }
+  if (acc.episodes) atomicAdd(&n_valid, (unsigned long long)acc.episodes);
+  __syncthreads();
+  block_flush(acc, hist, &R.sums[j]);
+  const int64_t nv = (int64_t)n_valid;
+  cpr_eval_alpha* out = &R.out[j];
+  if (t == 0) {
+    out->alpha = R.tab_a ? R.tab_a[j] : R.cfg_alpha;
+    out->n = nv;
+  }
+  for (int c = 0; c < CPR_EVAL_COLUMNS; ++c) {
+    double mean = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {
+      __syncthreads();  // p's readers of the previous round are done
+      p[t] = eval_partial(recs, stride, count, t, c, pass == 1, mean);
+      __syncthreads();
+      for (int off = kEvalThreads / 2; off > 0; off >>= 1) {
+        eval_tree_level(p, t, off);
+        __syncthreads();
+      }
+      if (pass == 0)
+        mean = eval_mean(p[0], nv);
+      else if (t == 0)
+        out->std[c] = eval_std(p[0], nv);
+    }
+    if (t == 0) out->mean[c] = mean;
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void k_lane_assign(LaneAssign A, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (A.mask == nullptr || A.mask[i]) {
     const uint64_t ep = A.eps ? A.eps[i] : (uint64_t)i;
-    const int32_t j = lane_alpha_index(A.seed, ep, A.n_alpha);
+    const int32_t j = lane_alpha_entry(A.schedule, A.seed, ep, A.n_alpha);
     A.lane_t[i] = A.tab_t[j];
     A.lane_alpha[i] = A.tab_a[j];
     A.dense_acc[i] = 0.0;
@@ -231,6 +346,17 @@ hipError_t launch_policy_collect(const PolCollect& C, int64_t n, hipStream_t st)
 hipError_t launch_lane_assign(const LaneAssign& A, int64_t n, hipStream_t st) {
   hipLaunchKernelGGL(k_lane_assign, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                      st, A, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_eval_collect(const EvalCollect& C, int64_t n, hipStream_t st) {
+  hipLaunchKernelGGL(k_eval_collect, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                     st, C, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_eval_reduce(const EvalReduce& R, hipStream_t st) {
+  hipLaunchKernelGGL(k_eval_reduce, dim3((unsigned)R.n_alpha), dim3(kEvalThreads), 0, st, R);
   return hipGetLastError();
 }
 

@@ -26,6 +26,15 @@ __host__ __device__ inline int32_t lane_alpha_index(uint64_t seed, uint64_t epis
   return i < n_alpha - 1 ? i : n_alpha - 1;
 }
 
+// the table entry of episode `episode` under a schedule (enum cpr_alpha_schedule):
+// CPR_SCHEDULE_CYCLE is itertools.cycle over the table (wrappers.py:186-193) as a function of
+// the episode id alone, entry episode mod n_alpha; anything else the keyed choice above
+__host__ __device__ inline int32_t lane_alpha_entry(int32_t schedule, uint64_t seed,
+                                                    uint64_t episode, int32_t n_alpha) {
+  if (schedule == CPR_SCHEDULE_CYCLE) return (int32_t)(episode % (uint64_t)n_alpha);
+  return lane_alpha_index(seed, episode, n_alpha);
+}
+
 // what the wrappers read of one engine step (engine.ml:223-241)
 struct GymStepInfo {
   double reward;    // engine.ml:223

@@ -116,6 +116,7 @@ struct LaneAssign {
   const uint64_t* eps;
   uint64_t seed;
   int32_t n_alpha;
+  int32_t schedule;       // enum cpr_alpha_schedule (lane_env.h lane_alpha_entry)
   const uint64_t* tab_t;  // [n_alpha] alpha_threshold of each entry
   const double* tab_a;    // [n_alpha]
   uint64_t* lane_t;       // [n]
@@ -124,6 +125,58 @@ struct LaneAssign {
   double* out_alpha;      // [n]
 };
 hipError_t launch_lane_assign(const LaneAssign& A, int64_t n, hipStream_t st);
+
+// per-step bookkeeping of cpr_eval_net over n lanes (device pointers): the wrapped and shaped
+// reward as in PolCollect, summed per lane in step order; at a done of an episode of the set
+// [first, first + n_set) one cpr_eval_record at slot episode - first
+struct EvalCollect {
+  const double* reward;
+  const uint8_t* done;
+  const double* era;
+  const double* erd;
+  const double* eprog;
+  const double* ect;
+  const double* est;
+  const int64_t* esteps;
+  const int64_t* eacts;
+  const int32_t* hh;
+  const uint32_t* status;
+  int32_t orphans_from_progress;
+  uint64_t* ep;    // lane cursors: episode id, episode step index
+  int64_t* step;
+  uint8_t* mask;   // reset mask of this step
+  double* ep_reward;  // [n] erw_episode_reward of the lane's episode so far
+  // lane env (null lane_alpha: the engine's reward, every episode at cfg_alpha, entry 0)
+  int32_t gym_reward, reward_shape;
+  double dense_target;
+  const double* lane_alpha;
+  double* dense_acc;
+  double cfg_alpha;
+  int32_t n_alpha, schedule;
+  uint64_t seed;
+  // the set and its outputs
+  uint64_t first;
+  int64_t n_set;
+  cpr_eval_record* records;       // [n_set]
+  unsigned long long* finished;   // episodes of the set that have finished
+};
+hipError_t launch_eval_collect(const EvalCollect& C, int64_t n, hipStream_t st);
+
+// After the loop, one workgroup per alpha j < n_alpha over the records at slots s with
+// (first + s) mod n_alpha = j: that alpha's cpr_summary (sums, zeroed by the caller) and
+// cpr_eval_alpha (eval.h has the order).
+struct EvalReduce {
+  const cpr_eval_record* records;
+  uint64_t first;
+  int64_t per_alpha;      // records of each alpha
+  int32_t n_alpha;
+  const double* tab_a;    // [n_alpha] the table; null: cfg_alpha
+  double cfg_alpha;
+  cpr_summary* sums;      // [n_alpha]
+  cpr_eval_alpha* out;    // [n_alpha]
+};
+hipError_t launch_eval_reduce(const EvalReduce& R, hipStream_t st);
+
 // after the last step: activations of the episodes still running (acts[i] - acts0[i])
 hipError_t launch_policy_tail(const int64_t* acts, const int64_t* acts0, int64_t n,
                               cpr_summary* sum, hipStream_t st);

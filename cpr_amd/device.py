@@ -314,6 +314,25 @@ class PolicyNet:
         return outs[0], outs[1][:, 0]
 
 
+class EvalResult:
+    """What ``Batch.evaluate_net`` returns. ``per_alpha``: one dict per table entry with
+    ``alpha``, ``n`` (valid episodes), ``mean_<column>`` / ``std_<column>`` for the columns of
+    ``_lib.EVAL_COLUMNS`` and that alpha's ``summary`` (a ``Summary``); ``stats``: the same
+    numbers as a structured array (``_lib.EVAL_ALPHA_DTYPE``); ``records``: a structured array
+    (``_lib.EVAL_RECORD_DTYPE``), record i is episode first_episode + i, or None; ``total``:
+    the sum of the per-alpha summaries."""
+
+    def __init__(self, stats, summaries, records, total):
+        self.stats, self.summaries, self.records, self.total = stats, summaries, records, total
+        self.per_alpha = []
+        for st, sm in zip(stats, summaries):
+            d = {"alpha": float(st["alpha"]), "n": int(st["n"]), "summary": sm}
+            for c, name in enumerate(L.EVAL_COLUMNS):
+                d["mean_" + name] = float(st["mean"][c])
+                d["std_" + name] = float(st["std"][c])
+            self.per_alpha.append(d)
+
+
 class Batch:
     def __init__(self, config, ctx=None, keep=None):
         self.ctx = ctx or default_context()
@@ -326,6 +345,7 @@ class Batch:
         self.obs_len = self.observation_spec()[0]
         self._coverage_warned = False
         self._lane_env = False
+        self._n_alpha = 1  # table entries of the lane env: evaluate_net's result count
 
     def close(self):
         if self.handle:
@@ -547,15 +567,21 @@ class Batch:
                    "dense_per_progress": L.GYM_REWARD_DENSE_PER_PROGRESS}
     REWARD_SHAPES = {"none": L.SHAPE_NONE, "per_alpha": L.SHAPE_PER_ALPHA, "cut": L.SHAPE_CUT}
 
+    SCHEDULES = {"choice": L.SCHEDULE_CHOICE, "cycle": L.SCHEDULE_CYCLE}
+
     def set_lane_env(self, alphas=None, alpha_column=None, reward="engine", shape="none",
-                     dense_target=None):
+                     dense_target=None, schedule="choice"):
         """The assumption schedule and reward wrappers of cpr-v0 on the lanes, before the
         first reset or rollout. ``alphas``: the table an episode's alpha is chosen from by
         (seed, episode) (None: the config's alpha); ``alpha_column``: the column of the
         network's extras that a rollout feeds with the lane's alpha (None: constants only);
         ``reward`` in GYM_REWARDS, ``shape`` in REWARD_SHAPES ("per_alpha" is r / alpha, "cut"
         is ppo.py's); ``dense_target``: episode_len of "dense_per_progress". They apply to
-        ``rollout_net``'s reward; ``step`` keeps the engine's."""
+        ``rollout_net``'s reward; ``step`` keeps the engine's. ``schedule``: "choice" (an entry
+        per episode by (seed, episode), ppo.py's random.choice) or "cycle" (episode e runs at
+        entry e mod len(alphas), the reference wrapper's itertools.cycle)."""
+        if schedule not in self.SCHEDULES:
+            raise ValueError(f"schedule: expected one of {sorted(self.SCHEDULES)}")
         if reward not in self.GYM_REWARDS:
             raise ValueError(f"reward: expected one of {sorted(self.GYM_REWARDS)}")
         if shape not in self.REWARD_SHAPES:
@@ -574,6 +600,39 @@ class Batch:
         e.dense_target = 0.0 if dense_target is None else float(dense_target)
         L.check(L.lib().cpr_lane_env_set(self.handle, ctypes.byref(e)))
         self._lane_env = True
+        L.check(L.lib().cpr_lane_env_schedule(self.handle, self.SCHEDULES[schedule]))
+        self._n_alpha = 1 if tab is None else int(tab.size)
+
+    # ---- evaluation (cpr_eval_net, cpr_policy_net_copy; DESIGN.md §4.14 "Evaluation")
+    def evaluate_net(self, episodes_per_alpha, first_episode=0, deterministic=True,
+                     check_every=None, records=True):
+        """Whole episodes of the batch's network, one result per alpha (cpr_eval_net): the
+        episode set [first_episode, first_episode + n_alpha * episodes_per_alpha), every lane
+        reset first, the reward of the lane env summed per episode. The results depend on the
+        seed, the set and the network only, not on the lane count or on ``check_every`` (the
+        steps between two looks at the finished-episode counter; None: max_steps). Returns an
+        ``EvalResult``. Afterwards ``step`` and the rollouts need a ``reset``."""
+        a = self._n_alpha
+        o = L.EvalOptsC()
+        o.episodes_per_alpha = int(episodes_per_alpha)
+        o.first_episode = int(first_episode)
+        o.deterministic = 1 if deterministic else 0
+        o.check_every = 0 if check_every is None else int(check_every)
+        n_set = a * max(0, o.episodes_per_alpha)
+        rec = np.zeros(n_set, dtype=L.EVAL_RECORD_DTYPE) if records else None
+        stats = np.zeros(a, dtype=L.EVAL_ALPHA_DTYPE)
+        sums = (L.Summary * a)()
+        total = L.Summary()
+        L.check(L.lib().cpr_eval_net(self.handle, ctypes.byref(o), L.ptr(rec), L.ptr(stats),
+                                     ctypes.cast(sums, ctypes.c_void_p), ctypes.byref(total)))
+        return EvalResult(stats, list(sums), rec, total)
+
+    def copy_policy_net_from(self, other):
+        """Take ``other``'s current weights (cpr_policy_net_copy): device to device on the
+        context's stream, for an eval batch beside the batch being trained. Shapes and
+        extras must match a network this batch already has; its Adam state is zeroed."""
+        L.check(L.lib().cpr_policy_net_copy(self.handle, other.handle))
+        self._net = getattr(other, "_net", None)
 
     def lane_alpha(self):
         """alpha of every lane's current episode (cpr_lane_alpha)."""

@@ -168,6 +168,7 @@ def device_env_fn(
     reward="sparse_relative",
     normalize_reward=True,
     shape=None,
+    eval=False,
 ):
     """``env_fn`` (cpr-v0) over ``n_envs`` device lanes: returns ``(batch, extras)``, a
     configured ``device.Batch`` whose lane env (``Batch.set_lane_env``) holds the assumption
@@ -181,7 +182,13 @@ def device_env_fn(
     a sequence (one entry is chosen per episode, like ppo.py's ``random.choice``; the
     reference's wrapper cycles a sequence instead) or a zero-argument callable. Deviation: a
     callable is sampled 4,096 times into the table here, and episodes choose among those
-    draws by (seed, episode). Gamma is fixed, as in ppo.py."""
+    draws by (seed, episode). Gamma is fixed, as in ppo.py.
+
+    ``eval=True`` builds ppo.py's eval env for ``Batch.evaluate_net``: a sequence ``alpha``
+    cycles (episode e runs at entry e mod len(alpha), the reference wrapper's
+    itertools.cycle; ppo.py's Range is the caller's ``numpy.arange`` grid passed as a list),
+    and the reward shape is "per_alpha" whatever ``shape`` says (ppo.py:218-219). Give an eval
+    batch its own ``seed``, or it replays the training batch's draws."""
     from . import _lib as L
     from . import device
 
@@ -197,7 +204,11 @@ def device_env_fn(
     if reward not in ("sparse_relative", "sparse_per_progress", "dense_per_progress"):
         raise KeyError(reward)
     dense = reward == "dense_per_progress"
-    if shape is None:
+    if eval:
+        if callable(alpha):
+            raise ValueError("device_env_fn: eval=True needs a float or a sequence of alphas")
+        shape = "per_alpha"
+    elif shape is None:
         shape = "per_alpha" if normalize_reward else "none"
     cfg, keep = device.make_config(
         protocol=proto.protocol_id,
@@ -217,7 +228,8 @@ def device_env_fn(
     )
     batch = device.Batch(cfg, ctx=ctx, keep=keep)
     batch.set_lane_env(alphas=table, alpha_column=None if pretend_alpha is not None else 0,
-                       reward=reward, shape=shape, dense_target=episode_len if dense else None)
+                       reward=reward, shape=shape, dense_target=episode_len if dense else None,
+                       schedule="cycle" if eval else "choice")
     extras = (table[0] if pretend_alpha is None else float(pretend_alpha),
               float(gamma) if pretend_gamma is None else float(pretend_gamma))
     return batch, extras

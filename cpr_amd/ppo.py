@@ -82,15 +82,47 @@ def unflatten_grads(net, flat):
     return out
 
 
-def train(batch, iterations, n_steps, options=None, lr_schedule=None):
+def eval_statistics(result):
+    """EvalCallback's logged numbers (ppo.py:341-374) of an ``EvalResult`` with records: the
+    mean and the standard deviation (pandas' ddof = 1; NaN for a single record) of every
+    column of ``_lib.EVAL_COLUMNS`` over all valid records, the alpha column dropped, computed
+    here on the host: {"eval/mean_<column>": ..., "eval/std_<column>": ...}, and under
+    "eval/per_alpha" the per-alpha table (``EvalResult.per_alpha``)."""
+    rec = result.records
+    rec = rec[(rec["status"] & L.ST_INVALID) == 0]
+    out = {}
+    for name in L.EVAL_COLUMNS:
+        x = rec[name].astype(np.float64)
+        out["eval/mean_" + name] = float(np.mean(x)) if x.size else float("nan")
+        out["eval/std_" + name] = float(np.std(x, ddof=1)) if x.size > 1 else float("nan")
+    out["eval/per_alpha"] = result.per_alpha
+    return out
+
+
+def train(batch, iterations, n_steps, options=None, lr_schedule=None, eval_batch=None,
+          eval_freq=1, eval_start=0, eval_episodes_per_alpha=1):
     """``iterations`` PPO iterations of ``n_steps`` steps per lane on ``batch`` (which has a
     network set): yields (summary, statistics dict) per iteration. ``lr_schedule(x)``, x the
     fraction of training remaining (1 at the start; ppo.py:382-387), gives the iteration's
-    learning rate; None keeps ``options.lr``."""
+    learning rate; None keeps ``options.lr``.
+
+    ``eval_batch`` (a separate batch on the same context, e.g. ``envs.device_env_fn(...,
+    eval=True)``; None: no evaluation, nothing changes): at the start of iteration ``it``
+    with ``it >= eval_start and it % eval_freq == 0`` (EvalCallback._on_rollout_start) it
+    takes ``batch``'s weights (``copy_policy_net_from``) and evaluates
+    ``eval_episodes_per_alpha`` whole episodes per alpha, deterministic, from episode 0 every
+    time (common random numbers between evaluations); the iteration's statistics gain
+    ``eval_statistics``' keys. The training batch is not touched by it."""
     opts = dataclasses.replace(options) if options is not None else PPOOptions()
     for it in range(int(iterations)):
+        ev = None
+        if eval_batch is not None and it >= eval_start and it % eval_freq == 0:
+            eval_batch.copy_policy_net_from(batch)
+            ev = eval_statistics(eval_batch.evaluate_net(eval_episodes_per_alpha))
         if lr_schedule is not None:
             opts.lr = float(lr_schedule(1.0 - it / float(iterations)))
         summary, stats = batch.ppo_iterate(n_steps, opts)
         stats["lr"] = opts.lr
+        if ev is not None:
+            stats.update(ev)
         yield summary, stats

@@ -50,7 +50,8 @@ enum cpr_status {
   CPR_E_UNSUPPORTED = -2,   /* configuration the device engine does not implement */
   CPR_E_HIP = -3,           /* HIP runtime error */
   CPR_E_CAPACITY = -4,      /* lane capacity exceeded */
-  CPR_E_STATE = -5          /* call order violated (step before reset, ...) */
+  CPR_E_STATE = -5,         /* call order violated (step before reset, ...) */
+  CPR_E_INTERNAL = -6       /* the library contradicted one of its own invariants */
 };
 
 enum cpr_protocol {
@@ -640,6 +641,104 @@ typedef struct cpr_rollout_env_out {
 int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
                         const cpr_rollout_net_out* out, const cpr_rollout_env_out* env_out,
                         int outputs_on_device, cpr_summary* summary);
+
+/* A cyclic assumption schedule (added within v11; a batch that never calls this launches what
+ * it did before). CPR_SCHEDULE_CHOICE is the keyed random.choice above. Under
+ * CPR_SCHEDULE_CYCLE episode e runs at table entry e mod n_alpha: itertools.cycle over the
+ * table (AssumptionScheduleWrapper, wrappers.py:186-193) as a function of the episode id
+ * alone, so it depends neither on the lane count nor on how a run is cut into calls.
+ * Everything that follows the lane alpha follows it under either schedule. Callable when
+ * cpr_lane_env_set is: before the batch's first reset or rollout (CPR_E_STATE afterwards);
+ * cpr_lane_env_set keeps the schedule. CPR_E_INVALID_ARG: an unknown schedule. */
+enum cpr_alpha_schedule { CPR_SCHEDULE_CHOICE = 0, CPR_SCHEDULE_CYCLE = 1 };
+int cpr_lane_env_schedule(cpr_batch* b, int schedule);
+
+/* Evaluation of the batch's network (added within v11): EvalCallback + evaluate_policy of
+ * experiments/train/ppo.py:296-374,421-450 and experiments/rl-eval. A fixed set of whole
+ * episodes, one result per alpha.
+ *
+ * Episode set. A = the lane env's n_alpha (1 without a lane env: cfg.alpha). The set is
+ * [first_episode, first_episode + A episodes_per_alpha); under CPR_SCHEDULE_CYCLE every
+ * alpha gets exactly episodes_per_alpha of them. The call resets every lane (lane i to
+ * episode first_episode + i), then steps all lanes with the network; a lane whose episode ends
+ * restarts at its id + n_lanes, as in the rollout, also beyond the set (whatever episodes
+ * outside the set produce is discarded). The call ends when every episode of the set has
+ * finished: the host reads a device counter every check_every steps (0: every max_steps
+ * steps). ceil(set / n_lanes) max_steps steps always suffice; a counter that disagrees after
+ * that many is CPR_E_INTERNAL. The results depend on the seed, the set and the network only,
+ * not on n_lanes or check_every.
+ *
+ * One record per episode of the set, at slot episode - first_episode: the reward is the wrapped
+ * and shaped reward of the lane env (the engine's without one) summed in step order from 0
+ * (EpisodeRecorderWrapper's erw_episode_reward, wrappers.py:245-266); the other fields are
+ * the step infos of the episode's last step. height is the head height the summary's orphans
+ * are counted against (B_k, Tailstorm: (int64)progress).
+ *
+ * Per alpha (entry j of the table; slots s with (first_episode + s) mod A = j, in slot order
+ * r_0, r_1, ...): a cpr_summary of those records by the rule of every other summary (an
+ * episode with CPR_ST_INVALID bits: steps, activations and `invalid` only), and the mean and
+ * unbiased standard deviation of the five columns EvalCallback logs, over the n valid records,
+ * in f64 with this order (one rounding per operation, no fused multiply-add):
+ *   p_t = 0 + sum of x(r_k) over valid r_k, k = t, t + 256, t + 512, ... in that order, t < 256
+ *   for off = 128, 64, ..., 1: p_t = p_t + p_{t + off} for every t < off
+ *   mean = p_0 / n
+ *   the same with (x(r_k) - mean) (x(r_k) - mean) in place of x(r_k): std = sqrt(p_0 / (n - 1))
+ * mean is NaN for n = 0 and std for n < 2 (pandas). x of column CPR_EVAL_N_ACTIVATIONS is
+ * (double)episode_n_activations.
+ *
+ * CPR_E_STATE without a network; CPR_E_INVALID_ARG: episodes_per_alpha < 1, check_every < 0;
+ * CPR_E_UNSUPPORTED: FC16, cfg.max_steps <= 0 (no bound on an episode), a table of more than
+ * one alpha under CPR_SCHEDULE_CHOICE (its alphas do not get equal shares of a set). After
+ * the call the lanes stand in arbitrary later episodes: cpr_step, cpr_rollout and
+ * cpr_rollout_net are CPR_E_STATE until a cpr_reset of every lane or the next cpr_eval_net.
+ * Weights, Adam state and the update count are untouched. Synchronous; the launch timer
+ * covers the whole call. */
+typedef struct cpr_eval_opts {
+  int64_t episodes_per_alpha; /* >= 1 */
+  uint64_t first_episode;
+  int32_t deterministic;      /* EvalCallback: 1 */
+  int64_t check_every;        /* steps between looks at the finished-episode counter; 0: max_steps */
+} cpr_eval_opts;
+typedef struct cpr_eval_record {
+  uint64_t episode;
+  double alpha;
+  double episode_reward;
+  double episode_sim_time;
+  double episode_chain_time;
+  double episode_progress;
+  double reward_attacker;
+  double reward_defender;
+  int64_t episode_n_activations;
+  int64_t episode_n_steps;
+  int64_t height;
+  int32_t alpha_index;
+  uint32_t status;            /* enum cpr_episode_status bits */
+} cpr_eval_record;
+enum cpr_eval_column {
+  CPR_EVAL_REWARD = 0, CPR_EVAL_SIM_TIME = 1, CPR_EVAL_CHAIN_TIME = 2, CPR_EVAL_PROGRESS = 3,
+  CPR_EVAL_N_ACTIVATIONS = 4
+};
+#define CPR_EVAL_COLUMNS 5
+typedef struct cpr_eval_alpha {
+  double alpha;
+  int64_t n;                  /* valid episodes */
+  double mean[CPR_EVAL_COLUMNS];
+  double std[CPR_EVAL_COLUMNS];
+} cpr_eval_alpha;
+/* Host pointers: records NULL or [A episodes_per_alpha]; per_alpha [A]; per_alpha_summary
+ * NULL or [A] (overwritten); total NULL or one summary (overwritten): the field-wise sum of
+ * the per-alpha summaries. */
+int cpr_eval_net(cpr_batch* b, const cpr_eval_opts* opts, cpr_eval_record* records,
+                 cpr_eval_alpha* per_alpha, cpr_summary* per_alpha_summary, cpr_summary* total);
+
+/* The weights of src into dst, device to device on the context's stream, no host round trip:
+ * the reference's separate eval_env (ppo.py:421-450) takes the training batch's weights this
+ * way. Both batches belong to one context. A dst without a network acquires src's shapes
+ * (checked like cpr_policy_net_set, the LDS check included); otherwise depth, widths, n_extra
+ * and the extras must be equal (CPR_E_INVALID_ARG; so are different observation or action
+ * widths and different contexts). dst's Adam state and update count are zeroed as after
+ * cpr_policy_net_set; src is unchanged. CPR_E_STATE: src has no network. */
+int cpr_policy_net_copy(cpr_batch* dst, cpr_batch* src);
 
 /* The learner (added within v11; a batch that never calls these launches what it did before):
  * SB3's PPO.train (experiments/train/ppo.py:399-451) on the batch's device weights.

@@ -308,6 +308,20 @@ let ppo_iterate =
 
 let policy_net_get = foreign "cpr_policy_net_get" (ptr batch @-> ptr void @-> returning int)
 
+(* evaluation (added within ABI v11): the cyclic assumption schedule (0 = choice, 1 = cycle),
+   whole episodes with per-alpha results (cpr_eval_opts, cpr_eval_record and cpr_eval_alpha
+   are untyped pointers to caller-built C structs) and the device-to-device weight copy *)
+let lane_env_schedule = foreign "cpr_lane_env_schedule" (ptr batch @-> int @-> returning int)
+
+let eval_net =
+  foreign
+    "cpr_eval_net"
+    (ptr batch @-> ptr void @-> ptr void @-> ptr void @-> ptr summary @-> ptr summary
+    @-> returning int)
+;;
+
+let policy_net_copy = foreign "cpr_policy_net_copy" (ptr batch @-> ptr batch @-> returning int)
+
 let policy_actions =
   foreign
     "cpr_policy_actions"

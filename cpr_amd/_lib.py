@@ -72,6 +72,7 @@ POLICY_TABLE = 4
 POLICY_RANDOM = 5  # loop tasks on the event engine (cpr_protocols.ml:658-782)
 
 PROTO_FC16 = 4  # gym/rust/src/fc16.rs abstract model (fused episodes)
+PROTO_FC16_ENV = 5  # the same model with lockstep lanes: reset / step, networks, the learner
 FC16_POLICY_HONEST = 0
 FC16_POLICY_SM1 = 1
 FC16_POLICY_TABLE = 2
@@ -539,6 +540,7 @@ EXPORTS = [
     "cpr_eval_net",
     "cpr_policy_net_copy",
     "cpr_rollout_net_env",
+    "cpr_rollout_net_fused",
     "cpr_gae",
     "cpr_ppo_opts_default",
     "cpr_ppo_gradients",
@@ -601,6 +603,7 @@ def _declare(L):
     L.cpr_policy_net_copy.argtypes = [vp, vp]
     L.cpr_rollout_net_env.argtypes = [vp, ctypes.c_int64, ctypes.c_int, P(RolloutNetOut),
                                       P(RolloutEnvOut), ctypes.c_int, P(Summary)]
+    L.cpr_rollout_net_fused.argtypes = [vp, P(ctypes.c_int32)]
     L.cpr_gae.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp,
                           ctypes.c_int]
     L.cpr_ppo_opts_default.argtypes = [P(PpoOptsC)]

@@ -184,7 +184,10 @@ struct cpr_batch {
   DevBuf bk_lmem, bk_slots;  // lockstep lanes: n_lanes x bk_bytes, n_lanes slots
   int64_t bk_bytes = 0;
   ts::TsParams TP;       // CPR_PROTO_TAILSTORM (shares bk_lmem / bk_slots)
-  fc16::Fc16Params FP;   // CPR_PROTO_FC16
+  fc16::Fc16Params FP;   // CPR_PROTO_FC16, CPR_PROTO_FC16_ENV
+  bool is_fc16 = false;  // either of them: the fused-episode kernel k_fc16_episodes
+  bool fc16_env = false; // CPR_PROTO_FC16_ENV: lockstep lanes over bk_slots (Fc16Slot)
+  bool roll_fused = false;  // the last cpr_rollout_net(_env) ran as k_fc16_rollout_net
   bool is_ev = false;    // B_k or Tailstorm event-engine lanes
   // Nakamoto fused episodes: exact re-runs of flagged episodes on the event engine
   bool has_rerun = false;
@@ -839,8 +842,8 @@ int cpr_batch_create(cpr_ctx* ctx, const cpr_config* cfg, cpr_batch** out) {
   memset(&TP, 0, sizeof(TP));
   fc16::Fc16Params FP;
   memset(&FP, 0, sizeof(FP));
-  int rc = cfg->protocol == CPR_PROTO_FC16 ? validate_fc16(cfg, &FP)
-                                           : validate(cfg, &P, &EP, &BP, &TP);
+  const bool is_fc16 = cfg->protocol == CPR_PROTO_FC16 || cfg->protocol == CPR_PROTO_FC16_ENV;
+  int rc = is_fc16 ? validate_fc16(cfg, &FP) : validate(cfg, &P, &EP, &BP, &TP);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   cpr_batch* b = new cpr_batch;
@@ -851,6 +854,8 @@ int cpr_batch_create(cpr_ctx* ctx, const cpr_config* cfg, cpr_batch** out) {
   b->BP = BP;
   b->TP = TP;
   b->FP = FP;
+  b->is_fc16 = is_fc16;
+  b->fc16_env = cfg->protocol == CPR_PROTO_FC16_ENV;
   b->eth_bytes = eth::eth_lane_bytes(EP.cap_b, EP.cap_e, EP.n);
   if (cfg->protocol == CPR_PROTO_BK) b->bk_bytes = bk::bk_lane_bytes(BP);
   if (cfg->protocol == CPR_PROTO_TAILSTORM) b->bk_bytes = ts::ts_lane_bytes(TP);
@@ -865,7 +870,7 @@ int cpr_batch_create(cpr_ctx* ctx, const cpr_config* cfg, cpr_batch** out) {
              (cfg->protocol == CPR_PROTO_ETHEREUM && cfg->policy == CPR_ETH_POLICY_TABLE)) {
     const size_t nb = (size_t)cfg->policy_table_dim * cfg->policy_table_dim * 2;
     b->table_host.assign(cfg->policy_table, cfg->policy_table + nb);
-  } else if (cfg->protocol == CPR_PROTO_FC16 && cfg->policy == CPR_FC16_POLICY_TABLE) {
+  } else if (is_fc16 && cfg->policy == CPR_FC16_POLICY_TABLE) {
     const size_t D = (size_t)cfg->policy_table_dim;
     b->table_host.assign(cfg->policy_table, cfg->policy_table + D * D * 3);
   } else if (cfg->protocol == CPR_PROTO_TAILSTORM && cfg->policy == CPR_TS_POLICY_TABLE) {
@@ -925,7 +930,7 @@ int cpr_batch_create(cpr_ctx* ctx, const cpr_config* cfg, cpr_batch** out) {
 // lanes the device holds at once for this batch's fused-episode kernel (before any launch)
 static int64_t batch_resident(cpr_batch* b) {
   const int64_t cus = b->ctx->cus;
-  if (b->cfg.protocol == CPR_PROTO_FC16) return cus * 8 * 256;
+  if (b->is_fc16) return cus * 8 * 256;
   if (b->cfg.protocol == CPR_PROTO_ETHEREUM || b->nak_ev) return cus * eth_blocks_per_cu() * 256;
   if (b->is_ev)
     return cus * (b->cfg.protocol == CPR_PROTO_TAILSTORM ? ts_blocks_per_cu() : bk_blocks_per_cu()) *
@@ -1415,7 +1420,7 @@ static bool rerun_hybrid(const cpr_batch* b, bool trace, NakParams* NP) {
 
 static int run_async(cpr_batch* b, int64_t n, uint64_t first, const TraceSource* tr,
                      cpr_summary* sum_dev, cpr_episode_record* rec_dev) {
-  if (b->cfg.protocol == CPR_PROTO_FC16) return run_async_fc16(b, n, first, tr, sum_dev, rec_dev);
+  if (b->is_fc16) return run_async_fc16(b, n, first, tr, sum_dev, rec_dev);
   if (b->cfg.protocol == CPR_PROTO_ETHEREUM || b->nak_ev)
     return run_async_eth(b, n, first, tr, sum_dev, rec_dev);
   if (b->is_ev) return run_async_bk(b, n, first, tr, sum_dev, rec_dev);
@@ -1809,6 +1814,7 @@ int cpr_replay(cpr_batch* b, const cpr_trace* t, cpr_summary* summary,
                cpr_episode_record* records, int records_on_device) {
   if (!b || !t || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
+  if (b->fc16_env) return fail(CPR_E_UNSUPPORTED, "FC16 episodes have no trace format");
   if (b->cfg.network == CPR_NET_ABSTRACT_GAMMA)
     return fail(CPR_E_UNSUPPORTED, "the abstract-gamma mode has no trace replay");
   if (t->n_episodes <= 0) return CPR_OK;
@@ -1836,8 +1842,7 @@ int cpr_node_outputs(cpr_batch* b, int64_t n, uint64_t first, const cpr_trace* t
                      double* node_rewards) {
   if (!b || !node_activations || !node_rewards) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
-  if (b->cfg.protocol == CPR_PROTO_FC16)
-    return fail(CPR_E_UNSUPPORTED, "FC16 episodes have no network nodes");
+  if (b->is_fc16) return fail(CPR_E_UNSUPPORTED, "FC16 episodes have no network nodes");
   if (b->cfg.network == CPR_NET_ABSTRACT_GAMMA)
     return fail(CPR_E_UNSUPPORTED, "the abstract-gamma mode has no exact event engine");
   if (n_nodes != network_nodes(b->cfg))
@@ -1930,6 +1935,7 @@ static int obs_len_of(const cpr_config& c) {
     case CPR_PROTO_BK: return 8;
     case CPR_PROTO_ETHEREUM: return 10;
     case CPR_PROTO_TAILSTORM: return 10;
+    case CPR_PROTO_FC16_ENV: return 3;
     default: return 4;
   }
 }
@@ -1963,7 +1969,19 @@ static int ensure_lockstep_bk(cpr_batch* b) {
   return ensure_common_lockstep(b, obs_len_of(b->cfg));
 }
 
+// CPR_PROTO_FC16_ENV: one zeroed Fc16Slot per lane, no per-lane region
+static int ensure_lockstep_fc16(cpr_batch* b) {
+  const int64_t n = b->cfg.n_lanes;
+  if (n <= 0) return fail(CPR_E_STATE, "batch has no lockstep lanes (cfg.n_lanes = 0)");
+  if (!b->bk_slots.p) {
+    HIP_TRY(b->bk_slots.ensure((size_t)n * fc16_slot_bytes()));
+    HIP_TRY(hipMemsetAsync(b->bk_slots.p, 0, (size_t)n * fc16_slot_bytes(), b->ctx->stream));
+  }
+  return ensure_common_lockstep(b, obs_len_of(b->cfg));
+}
+
 static int ensure_lockstep(cpr_batch* b) {
+  if (b->fc16_env) return ensure_lockstep_fc16(b);
   if (b->is_ev || b->is_eth) return ensure_lockstep_bk(b);
   const int64_t n = b->cfg.n_lanes;
   if (n <= 0) return fail(CPR_E_STATE, "batch has no lockstep lanes (cfg.n_lanes = 0)");
@@ -2074,7 +2092,9 @@ static int launch_lock_step(cpr_batch* b, const int32_t* act, const StepBuffers&
   hipStream_t st = b->ctx->stream;
   const double* tabs = (const double*)b->tabs_dev.p;
   const uint64_t* lt = lane_thresholds(b);
-  if (b->is_eth)
+  if (b->fc16_env)
+    HIP_TRY(launch_fc16_step(b->FP, b->cfg.seed, b->bk_slots.p, n, act, sb, st, lt));
+  else if (b->is_eth)
     HIP_TRY(launch_eth_step(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
                             b->bk_slots.p, n, act, b->cfg.unit_observation, tabs, b->tab_n, sb,
                             st, lt));
@@ -2124,7 +2144,9 @@ static int launch_lock_reset(cpr_batch* b, const uint8_t* dmask, const uint64_t*
     A.out_alpha = out_alpha;
     HIP_TRY(launch_lane_assign(A, n, st));
   }
-  if (b->is_eth)
+  if (b->fc16_env)
+    HIP_TRY(launch_fc16_reset(b->FP, b->cfg.seed, b->bk_slots.p, n, dmask, deps, obs, st, lt));
+  else if (b->is_eth)
     HIP_TRY(launch_eth_reset(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
                              b->bk_slots.p, n, dmask, deps, b->cfg.unit_observation, tabs,
                              b->tab_n, obs, st, lt));
@@ -2230,7 +2252,9 @@ int cpr_observe_fields(cpr_batch* b, int32_t* fields) {
   const size_t per = (size_t)obs_len_of(b->cfg) * 4;
   DevBuf tmp;
   HIP_TRY(tmp.ensure((size_t)n * per));
-  if (b->is_eth)
+  if (b->fc16_env)
+    HIP_TRY(launch_fc16_observe_fields(b->bk_slots.p, n, (int32_t*)tmp.p, st));
+  else if (b->is_eth)
     HIP_TRY(launch_eth_observe_fields(b->EP, (uint8_t*)b->bk_lmem.p, b->eth_bytes, b->bk_slots.p,
                                       n, (int32_t*)tmp.p, st));
   else if (b->cfg.protocol == CPR_PROTO_BK)
@@ -2252,6 +2276,9 @@ int cpr_policy_actions(cpr_batch* b, int32_t policy, const double* obs, int64_t 
                        int32_t* actions) {
   if (!b || !obs || !actions) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
+  if (b->fc16_env)
+    return fail(CPR_E_UNSUPPORTED, "FC16 env: the built-in policies read (a, h, fork) in the "
+                                   "fused episodes (cpr_run_episodes), not encoded observations");
   if (b->cfg.protocol == CPR_PROTO_TAILSTORM) {
     if (policy < 0 || policy > CPR_TS_POLICY_TABLE)
       return fail(CPR_E_INVALID_ARG, "unknown policy");
@@ -2338,7 +2365,7 @@ int cpr_observation_spec(cpr_batch* b, int32_t* obs_len, int32_t* n_actions, dou
   if (!b) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
   const double inf = __builtin_inf();
-  if (b->cfg.protocol == CPR_PROTO_FC16) {
+  if (b->is_fc16) {
     // fc16.rs:61-73: (a, h, fork index) each mapped x -> x / (1 + x); at most 4 actions
     if (obs_len) *obs_len = 3;
     if (n_actions) *n_actions = 4;
@@ -2519,6 +2546,9 @@ int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint
                 int outputs_on_device, cpr_summary* summary) {
   if (!b || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
+  if (b->fc16_env)
+    return fail(CPR_E_UNSUPPORTED, "FC16 env: the built-in policies run as fused episodes "
+                                   "(cpr_run_episodes); rollouts take a network (cpr_rollout_net)");
   if (b->env_table)
     return fail(CPR_E_UNSUPPORTED, "cpr_rollout (built-in policies) runs every lane at cfg.alpha; "
                                    "this batch has an alpha table (cpr_lane_env_set)");
@@ -2781,7 +2811,9 @@ int cpr_policy_net_forward(cpr_batch* b, const double* obs, int64_t n, int deter
 static int launch_lane_cursor(cpr_batch* b, const LaneCursor& c) {
   const int64_t n = b->cfg.n_lanes;
   hipStream_t st = b->ctx->stream;
-  if (b->is_eth)
+  if (b->fc16_env)
+    HIP_TRY(launch_fc16_cursor(b->bk_slots.p, n, c, st));
+  else if (b->is_eth)
     HIP_TRY(launch_eth_cursor(b->bk_slots.p, n, c, st));
   else if (b->cfg.protocol == CPR_PROTO_BK)
     HIP_TRY(launch_bk_cursor(b->bk_slots.p, n, c, st));
@@ -2812,6 +2844,9 @@ int cpr_lane_env_set(cpr_batch* b, const cpr_lane_env* env) {
     return fail(CPR_E_INVALID_ARG, "lane env: unknown gym_reward");
   if (env->reward_shape < CPR_SHAPE_NONE || env->reward_shape > CPR_SHAPE_CUT)
     return fail(CPR_E_INVALID_ARG, "lane env: unknown reward_shape");
+  if (env->gym_reward == CPR_GYM_REWARD_DENSE_PER_PROGRESS && b->fc16_env)
+    return fail(CPR_E_UNSUPPORTED, "lane env: the FC16 model has no progress target "
+                                   "(CPR_GYM_REWARD_DENSE_PER_PROGRESS)");
   if (env->gym_reward == CPR_GYM_REWARD_DENSE_PER_PROGRESS && !(env->dense_target > 0.0))
     return fail(CPR_E_INVALID_ARG, "lane env: dense_target <= 0");
   if (env->alpha_column < -1)
@@ -2989,10 +3024,56 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
     C.lane_alpha = (const double*)b->le_lane_a.p;
     C.dense_acc = (double*)b->le_acc.p;
   }
+  // FC16 env lanes with CPR_FC16_ROLLOUT_FUSED=1 (read at every call): every step, the
+  // bootstrap row and the tail in one kernel, unless its LDS does not fit
+  // the device. Off by default: it computes the same bits as the launch sequence below and is
+  // faster at 4,096 lanes, but loses to it at 65,536 lanes x 3 x 64
+  // (profiles/fc16_rollout_speed.json); CPR_FC16_ROLLOUT_FUSED=0 names the default
+#ifndef CPR_FC16_ROLLOUT_FUSED_DEFAULT
+#define CPR_FC16_ROLLOUT_FUSED_DEFAULT 0
+#endif
+  const char* fv = getenv("CPR_FC16_ROLLOUT_FUSED");
+  const bool want_fused = fv ? fv[0] != '0' : CPR_FC16_ROLLOUT_FUSED_DEFAULT != 0;
+  const bool fused = b->fc16_env && want_fused && fc16_rollout_net_fits(b->pn);
+  b->roll_fused = fused;
+  if (fused) {
+    Fc16Roll R = {};
+    R.P = b->FP;
+    R.seed = b->cfg.seed;
+    R.slots = b->bk_slots.p;
+    R.n = n;
+    R.n_steps = n_steps;
+    R.deterministic = deterministic ? 1 : 0;
+    R.fresh = fresh ? 1 : 0;
+    R.obs = D.obs;
+    R.action = D.action;
+    R.reward = D.reward;
+    R.done = D.done;
+    R.logp = D.logp;
+    R.value = D.value;
+    R.alpha = env ? DE.alpha : nullptr;
+    R.engine_reward = DE.engine_reward;
+    R.sum = (cpr_summary*)b->summary.p;
+    R.alpha_col = -1;
+    if (env) {
+      R.n_alpha = b->env.n_alpha;
+      R.schedule = b->schedule;
+      R.gym_reward = b->env.gym_reward;
+      R.reward_shape = b->env.reward_shape;
+      R.alpha_col = b->env.alpha_column;
+      R.dense_target = b->env.dense_target;
+      R.tab_t = (const uint64_t*)b->le_tab_t.p;
+      R.tab_a = (const double*)b->le_tab_a.p;
+      R.lane_t = (uint64_t*)b->le_lane_t.p;
+      R.lane_alpha = (double*)b->le_lane_a.p;
+      R.dense_acc = (double*)b->le_acc.p;
+    }
+    HIP_TRY(launch_fc16_rollout_net(b->pn, R, st));
+  }
   // the policy input of step t: l_obs before the first step, then where the reset kernel
   // of step t - 1 wrote every lane's observation (the caller's obs row, or l_obs)
   const double* in_obs = sb.obs;
-  for (int64_t t = 0; t < n_steps; ++t) {
+  for (int64_t t = 0; t < n_steps && !fused; ++t) {
     int32_t* act = D.action ? D.action + t * n : (int32_t*)b->l_act.p;
     io.obs = in_obs;
     io.action = act;
@@ -3011,7 +3092,7 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
     if (rc) return rc;
     in_obs = next_obs;
   }
-  if (D.value) {  // PPO's bootstrap: the value of the final observation
+  if (D.value && !fused) {  // PPO's bootstrap: the value of the final observation
     io.obs = in_obs;
     io.deterministic = 1;
     io.action = nullptr;
@@ -3019,12 +3100,13 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
     io.value = D.value + cells;
     HIP_TRY(launch_policy_forward(b->pn, io, st));
   }
-  // activations of the episodes still running
-  LaneCursor end = cur;
-  end.acts = (int64_t*)b->pn_acts.p;
-  rc = launch_lane_cursor(b, end);
-  if (rc) return rc;
-  HIP_TRY(launch_policy_tail(end.acts, cur.acts, n, C.sum, st));
+  if (!fused) {  // activations of the episodes still running
+    LaneCursor end = cur;
+    end.acts = (int64_t*)b->pn_acts.p;
+    rc = launch_lane_cursor(b, end);
+    if (rc) return rc;
+    HIP_TRY(launch_policy_tail(end.acts, cur.acts, n, C.sum, st));
+  }
   HIP_TRY(hipEventRecord(b->ev1, st));
   cpr_summary s;
   HIP_TRY(hipMemcpyAsync(&s, b->summary.p, sizeof(s), hipMemcpyDeviceToHost, st));
@@ -3054,6 +3136,13 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
   summary->status_other += s.status_other;
   summary->invalid += s.invalid;
   for (int i = 0; i < CPR_HIST_BINS; i++) summary->hist[i] += s.hist[i];
+  return CPR_OK;
+}
+
+int cpr_rollout_net_fused(cpr_batch* b, int32_t* fused) {
+  if (!b || !fused) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
+  *fused = b->roll_fused ? 1 : 0;
   return CPR_OK;
 }
 

@@ -13,6 +13,12 @@
 //   termination i    word i & 3 of block(j, TAG_FC16 | 0x100000 | i >> 2) < t_term
 // Thresholds are floor(p * 2^32), so each draw is an exact integer compare on both the
 // device and the oracle (tests/oracle_py.py fc16_episode).
+//
+// fc16_start / fc16_step are the model; fc16_episode (the fused episodes of CPR_PROTO_FC16
+// and CPR_PROTO_FC16_ENV) loops over them with a built-in or table policy, and the lockstep
+// env of CPR_PROTO_FC16_ENV (kernels_fc16.hip) steps them with the caller's action index
+// (fc16_action_name) and observes with fc16_observe. Host-compilable: tests/native_fc16
+// pins the functions against a pure-Python env.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,70 +65,118 @@ __host__ __device__ inline int32_t fc16_policy(const Fc16Params& P, int32_t a, i
   }
 }
 
+// The lane as an environment (the lockstep kernels and the fused network rollout of
+// kernels_fc16.hip): the state between two steps, and what one step pays.
+struct Fc16State {
+  int32_t a, h, fork;
+  int64_t steps;  // steps taken: the index of the next step's draws
+};
+
+struct Fc16Step {
+  int32_t reward, progress;
+  bool terminated;
+};
+
+// fc16.rs:75-81
+template <class St>
+__host__ __device__ inline Fc16State fc16_start(const Fc16Params& P, const St& S) {
+  Fc16State s{0, 0, IRRELEVANT, 0};
+  if ((uint64_t)S.block(0, TAG_FC16 | 1u).w0 < P.t_alpha)
+    s.a = 1;
+  else
+    s.h = 1;
+  return s;
+}
+
+// The env's action rule (fc16.rs:49-60, 182): index i selects from the offered list [Wait,
+// Adopt, Override if a > h, Match if a >= h]; an index beyond the list acts as entry 0, Wait.
+__host__ __device__ inline int32_t fc16_action_name(int32_t a, int32_t h, int32_t index) {
+  if (index == 1) return ADOPT;
+  if (index == 2) return a > h ? OVERRIDE : (a == h ? MATCH : WAIT);
+  if (index == 3) return a > h ? MATCH : WAIT;
+  return WAIT;
+}
+
+// fc16.rs:61-73: x / (1 + x) of (a, h, fork index)
+__host__ __device__ inline void fc16_observe(const Fc16State& s, double* o) {
+  const double x[3] = {(double)s.a, (double)s.h, (double)s.fork};
+  for (int k = 0; k < 3; ++k) o[k] = x[k] / (1.0 + x[k]);
+}
+
+// One step with the named action (fc16.rs:83-139, 177-196): the named action if the state
+// offers it, else the list's first entry Wait (fc16.rs:182: an out-of-range index acts as
+// index 0)
+template <class St>
+__host__ __device__ inline Fc16Step fc16_step(const Fc16Params& P, const St& S, Fc16State& s,
+                                              int32_t act) {
+  if ((act == OVERRIDE && !(s.a > s.h)) || (act == MATCH && !(s.a >= s.h))) act = WAIT;
+  const uint32_t j = (uint32_t)s.steps;
+  const Words4 w = S.block(j, TAG_FC16);
+  const bool mining = (uint64_t)w.w0 < P.t_alpha;
+  int32_t na, nh, nf, r = 0, g = 0;
+  if (act == ADOPT) {  // fc16.rs:131-137
+    na = mining ? 1 : 0;
+    nh = mining ? 0 : 1;
+    nf = IRRELEVANT;
+    g = s.h;
+  } else if (act == OVERRIDE) {  // fc16.rs:116-129
+    na = mining ? s.a - s.h : s.a - s.h - 1;
+    nh = mining ? 0 : 1;
+    nf = mining ? IRRELEVANT : RELEVANT;
+    r = g = s.h + 1;
+  } else if (act == MATCH || s.fork == ACTIVE) {  // fc16.rs:103-114
+    if (mining) {
+      na = s.a + 1;
+      nh = s.h;
+      nf = ACTIVE;
+    } else if ((uint64_t)w.w1 < P.t_gamma) {
+      na = s.a - s.h;
+      nh = 1;
+      nf = RELEVANT;
+      r = s.h;
+    } else {
+      na = s.a;
+      nh = s.h + 1;
+      nf = RELEVANT;
+    }
+  } else {  // Wait, no active match, fc16.rs:94-101
+    na = mining ? s.a + 1 : s.a;
+    nh = mining ? s.h : s.h + 1;
+    nf = mining ? IRRELEVANT : RELEVANT;
+  }
+  s.a = na;
+  s.h = nh;
+  s.fork = nf;
+  s.steps += 1;
+  // probabilistic termination: one Bernoulli(1/horizon) per unit of progress
+  bool term = false;
+  for (int32_t i = 0; i < g && !term; i += 4) {
+    const Words4 t = S.block(j, TAG_FC16 | 0x100000u | (uint32_t)(i >> 2));
+    const uint32_t tw[4] = {t.w0, t.w1, t.w2, t.w3};
+    for (int32_t q = 0; q < 4 && i + q < g; ++q) term |= (uint64_t)tw[q] < P.t_term;
+  }
+  return Fc16Step{r, g, term};
+}
+
 template <class St>
 __host__ __device__ inline Fc16Out fc16_episode(const Fc16Params& P, const St& S) {
+  Fc16State s = fc16_start(P, S);
   Fc16Out o{0, 0, 0, 0, 0, IRRELEVANT, 0u};
-  if ((uint64_t)S.block(0, TAG_FC16 | 1u).w0 < P.t_alpha)
-    o.a = 1;
-  else
-    o.h = 1;
-  for (uint32_t j = 0;; ++j) {
-    if ((int64_t)j >= P.max_steps) {
+  for (;;) {
+    if (s.steps >= P.max_steps) {
       o.status |= 32u;
-      return o;
+      break;
     }
-    // the named action if the state offers it, else the list's first entry Wait
-    // (fc16.rs:182: an out-of-range index acts as index 0)
-    int32_t act = fc16_policy(P, o.a, o.h, o.fork);
-    if ((act == OVERRIDE && !(o.a > o.h)) || (act == MATCH && !(o.a >= o.h))) act = WAIT;
-    const Words4 w = S.block(j, TAG_FC16);
-    const bool mining = (uint64_t)w.w0 < P.t_alpha;
-    int32_t na, nh, nf, r = 0, g = 0;
-    if (act == ADOPT) {  // fc16.rs:131-137
-      na = mining ? 1 : 0;
-      nh = mining ? 0 : 1;
-      nf = IRRELEVANT;
-      g = o.h;
-    } else if (act == OVERRIDE) {  // fc16.rs:116-129
-      na = mining ? o.a - o.h : o.a - o.h - 1;
-      nh = mining ? 0 : 1;
-      nf = mining ? IRRELEVANT : RELEVANT;
-      r = g = o.h + 1;
-    } else if (act == MATCH || o.fork == ACTIVE) {  // fc16.rs:103-114
-      if (mining) {
-        na = o.a + 1;
-        nh = o.h;
-        nf = ACTIVE;
-      } else if ((uint64_t)w.w1 < P.t_gamma) {
-        na = o.a - o.h;
-        nh = 1;
-        nf = RELEVANT;
-        r = o.h;
-      } else {
-        na = o.a;
-        nh = o.h + 1;
-        nf = RELEVANT;
-      }
-    } else {  // Wait, no active match, fc16.rs:94-101
-      na = mining ? o.a + 1 : o.a;
-      nh = mining ? o.h : o.h + 1;
-      nf = mining ? IRRELEVANT : RELEVANT;
-    }
-    o.a = na;
-    o.h = nh;
-    o.fork = nf;
-    o.reward += r;
-    o.progress += g;
-    o.steps += 1;
-    // probabilistic termination: one Bernoulli(1/horizon) per unit of progress
-    bool term = false;
-    for (int32_t i = 0; i < g && !term; i += 4) {
-      const Words4 t = S.block(j, TAG_FC16 | 0x100000u | (uint32_t)(i >> 2));
-      const uint32_t tw[4] = {t.w0, t.w1, t.w2, t.w3};
-      for (int32_t q = 0; q < 4 && i + q < g; ++q) term |= (uint64_t)tw[q] < P.t_term;
-    }
-    if (term) return o;
+    const Fc16Step t = fc16_step(P, S, s, fc16_policy(P, s.a, s.h, s.fork));
+    o.reward += t.reward;
+    o.progress += t.progress;
+    if (t.terminated) break;
   }
+  o.steps = s.steps;
+  o.a = s.a;
+  o.h = s.h;
+  o.fork = s.fork;
+  return o;
 }
 
 }  // namespace fc16

@@ -10,6 +10,7 @@
 #include "nakamoto_lane.h"
 #include "nak_fused.h"
 #include "fc16_lane.h"
+#include "policy_net.h"
 #include "summary.h"
 #include "ts_lane.h"
 
@@ -405,5 +406,50 @@ int run_episodes_blocks_per_cu(const NakParams& P, int32_t mode, bool recs);
 hipError_t launch_fc16_episodes(const fc16::Fc16Params& P, uint64_t seed, uint64_t first,
                                 int64_t n_eps, int64_t lanes, cpr_episode_record* recs,
                                 cpr_summary* sum, hipStream_t st);
+// the same lane as a lockstep env (CPR_PROTO_FC16_ENV): slots = n x fc16_slot_bytes(), zeroed;
+// observations of 3 doubles per lane
+hipError_t launch_fc16_reset(const fc16::Fc16Params& P, uint64_t seed, void* slots, int64_t n,
+                             const uint8_t* mask, const uint64_t* eps, double* obs,
+                             hipStream_t st, const uint64_t* lane_t = nullptr);
+hipError_t launch_fc16_step(const fc16::Fc16Params& P, uint64_t seed, void* slots, int64_t n,
+                            const int32_t* actions, const StepBuffers& b, hipStream_t st,
+                            const uint64_t* lane_t = nullptr);
+hipError_t launch_fc16_observe_fields(const void* slots, int64_t n, int32_t* f, hipStream_t st);
+hipError_t launch_fc16_cursor(const void* slots, int64_t n, const LaneCursor& c, hipStream_t st);
+size_t fc16_slot_bytes();
+// One call of cpr_rollout_net(_env) over the FC16 env lanes in one kernel
+// (k_fc16_rollout_net): n_steps steps of forward, step, collect and auto-reset per lane, the
+// bootstrap value row, the summary with the running episodes' activations. Device pointers;
+// outputs optional and step-major as cpr_rollout_net_out / cpr_rollout_env_out.
+struct Fc16Roll {
+  fc16::Fc16Params P;
+  uint64_t seed;
+  void* slots;
+  int64_t n, n_steps;
+  int32_t deterministic;
+  int32_t fresh;  // the call began with the batch's first reset: its activations count
+  double* obs;
+  int32_t* action;
+  double* reward;
+  uint8_t* done;
+  double* logp;
+  double* value;
+  double* alpha;
+  double* engine_reward;
+  cpr_summary* sum;
+  // lane env (lane_alpha null: none): the table, the lanes' thresholds, alphas and dense
+  // accumulators, read at the start and written back at the end
+  int32_t n_alpha, schedule, gym_reward, reward_shape, alpha_col;
+  double dense_target;
+  const uint64_t* tab_t;
+  const double* tab_a;
+  uint64_t* lane_t;
+  double* lane_alpha;
+  double* dense_acc;
+};
+// whether the kernel's LDS (policy_lds_bytes plus its static LDS) fits the device; a launch
+// that does not fit is refused (hipErrorInvalidValue) and the caller runs the launch sequence
+bool fc16_rollout_net_fits(const PolNet& N);
+hipError_t launch_fc16_rollout_net(const PolNet& N, const Fc16Roll& R, hipStream_t st);
 
 }  // namespace cpr

@@ -75,36 +75,13 @@ __global__ __launch_bounds__(kPolThreads) void k_policy_forward(PolNet N, PolIO 
   if (tid >= kPolRows || row >= io.n) return;
   const float* l = lg + tid * kPolLogitStride;
   const int na = N.n_actions;
-  float mf = l[0];
-  int am = 0;
-  for (int i = 1; i < na; ++i)
-    if (l[i] > mf) {  // the lowest index of the maximum
-      mf = l[i];
-      am = i;
-    }
-  const double m = (double)mf;
-  double S = 0.0;
-  for (int i = 0; i < na; ++i) S += exp((double)l[i] - m);
-  int a = am;
-  if (!io.deterministic) {
-    // u of the keyed block (episode, step index, TAG_POLICY): the smallest a with
-    // u S < sum_{i <= a} e_i, the last action if rounding leaves none
+  const PolChoice ch = pol_choose(l, na, io.deterministic != 0, [&](uint32_t* si) {
     const uint64_t ep = io.ep ? io.ep[row] : io.episode0 + (uint64_t)row;
-    const uint32_t si = io.step ? (uint32_t)io.step[row] : 0u;
-    const Words4 w = make_stream(io.seed, ep).block(si, TAG_POLICY);
-    const double uS = u53(w.w0, w.w1) * S;
-    double c = 0.0;
-    a = na - 1;
-    for (int i = 0; i < na; ++i) {
-      c += exp((double)l[i] - m);
-      if (uS < c) {
-        a = i;
-        break;
-      }
-    }
-  }
-  if (io.action) io.action[row] = a;
-  if (io.logp) io.logp[row] = ((double)l[a] - m) - log(S);
+    *si = io.step ? (uint32_t)io.step[row] : 0u;
+    return make_stream(io.seed, ep);
+  });
+  if (io.action) io.action[row] = ch.action;
+  if (io.logp) io.logp[row] = ch.logp;
   if (io.value) io.value[row] = (double)val[tid];
   if (io.logits)
     for (int i = 0; i < na; ++i) io.logits[row * na + i] = l[i];

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "cpr_stream.h"
 #include "policy_net.h"
 
 #pragma clang fp contract(off)
@@ -98,6 +99,48 @@ __device__ inline void pol_layer(const float* src, int sstride, const PolLayer& 
     }
   }
   __syncthreads();
+}
+
+// The forward's epilogue for one row, shared by k_policy_forward and the one-kernel FC16
+// rollout (k_fc16_rollout_net): from the row's f32 logits `l` the action (the lowest index of
+// the maximum, or the keyed sample at the draw key() returns) and its log-probability in f64.
+// key() -> Stream and step index of the row's draw; called only when sampling.
+struct PolChoice {
+  int32_t action;
+  double logp;
+};
+
+template <class Key>
+__device__ inline PolChoice pol_choose(const float* l, int na, bool deterministic, Key key) {
+  float mf = l[0];
+  int am = 0;
+  for (int i = 1; i < na; ++i)
+    if (l[i] > mf) {  // the lowest index of the maximum
+      mf = l[i];
+      am = i;
+    }
+  const double m = (double)mf;
+  double S = 0.0;
+  for (int i = 0; i < na; ++i) S += exp((double)l[i] - m);
+  int a = am;
+  if (!deterministic) {
+    // u of the keyed block (episode, step index, TAG_POLICY): the smallest a with
+    // u S < sum_{i <= a} e_i, the last action if rounding leaves none
+    uint32_t si = 0u;
+    const Stream st = key(&si);
+    const Words4 w = st.block(si, TAG_POLICY);
+    const double uS = u53(w.w0, w.w1) * S;
+    double c = 0.0;
+    a = na - 1;
+    for (int i = 0; i < na; ++i) {
+      c += exp((double)l[i] - m);
+      if (uS < c) {
+        a = i;
+        break;
+      }
+    }
+  }
+  return PolChoice{a, ((double)l[a] - m) - log(S)};
 }
 
 }  // namespace cpr

@@ -147,7 +147,7 @@ def make_config(
         c.policy = L.BK_POLICY_TABLE if protocol == L.PROTO_BK else L.TS_POLICY_TABLE
         c.policy_table = keep.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
         c.policy_table_dim = dim
-    elif table is not None and protocol == L.PROTO_FC16:
+    elif table is not None and protocol in (L.PROTO_FC16, L.PROTO_FC16_ENV):
         keep = np.ascontiguousarray(table, dtype=np.uint8).ravel()
         dim = int(round((keep.size // 3) ** 0.5))
         if dim * dim * 3 != keep.size:
@@ -718,6 +718,15 @@ class Batch:
         if outputs:
             arrays["done"] = arrays["done"].astype(bool)
         return s, arrays
+
+    def rollout_net_fused(self):
+        """Whether the batch's last ``rollout_net`` / ``ppo_iterate`` ran as one kernel
+        (cpr_rollout_net_fused; FC16 env batches) instead of the launch
+        sequence. Off by default; ``CPR_FC16_ROLLOUT_FUSED=1`` (read at every call) turns it
+        on, with the same outputs bit for bit."""
+        v = ctypes.c_int32()
+        L.check(L.lib().cpr_rollout_net_fused(self.handle, ctypes.byref(v)))
+        return bool(v.value)
 
     # ---- the learner (cpr_gae, cpr_ppo_*; DESIGN.md §4.14 "Learner")
     def gae(self, reward, done, value, gamma=0.99, lam=0.95, device=False, n_steps=None,

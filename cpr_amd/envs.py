@@ -113,6 +113,38 @@ class Core(Env):
         print(engine.to_string(self.ocaml_env))
 
 
+class FC16SSZwPT(Env):
+    """gym/rust/cpr_gym_rs/envs.py FC16SSZwPT over one device lane (CPR_PROTO_FC16_ENV), with
+    gymnasium's call shape: ``reset() -> (obs, {})``, ``step(a) -> (obs, r, terminated,
+    truncated, {})``. Actions index the offered list [Wait, Adopt, Override if a > h, Match if
+    a >= h]; an index beyond the list acts as Wait. ``max_steps`` (None: unbounded, as the
+    reference env) truncates an episode; ``truncated`` is the lane's capacity status. Episode
+    e of the env runs on the keyed stream of (seed, e)."""
+
+    def __init__(self, alpha=0.25, gamma=0.5, horizon=100, max_steps=None, seed=0, ctx=None):
+        from . import _lib as L
+        from . import device
+
+        cfg, keep = device.make_config(protocol=L.PROTO_FC16_ENV, alpha=alpha, gamma=gamma,
+                                       horizon=horizon, max_steps=max_steps, seed=seed,
+                                       policy=L.FC16_POLICY_HONEST, n_lanes=1)
+        self._capacity = L.ST_CAPACITY
+        self.batch = device.Batch(cfg, ctx=ctx, keep=keep)
+        self.action_space = Discrete(4)
+        self.observation_space = Box(np.zeros(3), np.ones(3))
+        self._episode = -1
+
+    def reset(self, *args, seed=None, options=None):
+        self._episode += 1
+        obs = self.batch.reset(episode_ids=[self._episode])
+        return obs[0], {}
+
+    def step(self, action):
+        obs, r, done, info = self.batch.step([int(action)])
+        truncated = bool(info["status"][0] & self._capacity)
+        return obs[0], float(r[0]), bool(done[0]) and not truncated, truncated, {}
+
+
 def env_fn(
     protocol="nakamoto",
     protocol_args=None,
@@ -201,6 +233,10 @@ def device_env_fn(
     ctor = getattr(protocols, protocol)
     args = dict(_protocol_args) if protocol_args is None else {**_protocol_args, **protocol_args}
     proto = ctor(**args)
+    fc16 = proto.protocol_id == L.PROTO_FC16_ENV
+    if fc16 and reward == "dense_per_progress":
+        raise ValueError("device_env_fn: the FC16 model has no progress target "
+                         "(dense_per_progress)")
     if reward not in ("sparse_relative", "sparse_per_progress", "dense_per_progress"):
         raise KeyError(reward)
     dense = reward == "dense_per_progress"
@@ -219,6 +255,7 @@ def device_env_fn(
         gamma=float(gamma),
         defenders=defenders,
         policy=L.POLICY_HONEST,
+        horizon=proto.params.get("horizon", 100.0),
         activation_delay=activation_delay,
         max_steps=episode_len * 100 if dense else episode_len,
         max_progress=episode_len if dense else None,

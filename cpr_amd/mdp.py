@@ -236,6 +236,53 @@ def fc16_table(alpha, gamma, *, dim=None, maximum_fork_length=20, horizon=100,
     return table.ravel()
 
 
+def fc16_action_name(a, h, index):
+    """The env's action rule (fc16.rs:49-60, 182): ``index`` selects from the offered list
+    [Wait, Adopt, Override if a > h, Match if a >= h]; beyond the list it acts as Wait."""
+    if index == 1:
+        return FC16_ADOPT
+    if index == 2:
+        return FC16_OVERRIDE if a > h else (FC16_MATCH if a == h else FC16_WAIT)
+    if index == 3:
+        return FC16_MATCH if a > h else FC16_WAIT
+    return FC16_WAIT
+
+
+def fc16_table_from_net(net, dim, extra=None, ctx=None):
+    """The `CPR_FC16_POLICY_TABLE` a deterministic ``device.PolicyNet`` plays in the FC16 env
+    (`CPR_PROTO_FC16_ENV`): every (a, h, fork) with a, h < dim as an observation row through
+    the device forward (argmax), the index mapped to an action name by the env's rule.
+    ``extra`` replaces the network's constants (e.g. another alpha). The table is exact
+    wherever a, h < dim: an episode of at most max_steps steps never leaves dim =
+    max_steps + 2."""
+    from . import _lib as L
+    from . import device
+
+    dim = int(dim)
+    if not 1 <= dim <= 256:
+        raise ValueError("dim: expected 1..256 (the table limit)")
+    if extra is not None:
+        if len(extra) != len(net.extra):
+            raise ValueError(f"extra: expected {len(net.extra)} values")
+        net = device.PolicyNet(net.pi, net.pi_head, net.vf, net.vf_head, extra=extra)
+    x = np.arange(dim, dtype=np.float64)
+    f = np.arange(3, dtype=np.float64)
+    a, h, fork = (g.ravel() for g in np.meshgrid(x, x, f, indexing="ij"))
+    obs = np.stack([a / (1.0 + a), h / (1.0 + h), fork / (1.0 + fork)], axis=1)
+    cfg, keep = device.make_config(protocol=L.PROTO_FC16_ENV, alpha=0.25, gamma=0.5, n_lanes=1,
+                                   policy=L.FC16_POLICY_HONEST)
+    b = device.Batch(cfg, ctx=ctx, keep=keep)
+    try:
+        b.set_policy_net(net)
+        index = b.policy_net_forward(obs, deterministic=True)[0]
+    finally:
+        b.close()
+    table = np.zeros(obs.shape[0], np.uint8)
+    for i, (ai, hi, ix) in enumerate(zip(a.astype(int), h.astype(int), index)):
+        table[i] = fc16_action_name(ai, hi, int(ix))
+    return table
+
+
 def _fc16_threshold(p):
     t = p * 4294967296.0
     return 0 if t <= 0 else (4294967296 if t >= 4294967296.0 else int(t))

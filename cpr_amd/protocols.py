@@ -98,3 +98,15 @@ def tailstorm(reward, k, subblock_selection, unit_observation):
                     subblock_selection=subblock_selection, selection_id=sel)
 
 tailstormjune = _not_on_device("tailstormjune")
+
+
+def fc16(horizon=100, unit_observation=True):
+    """The FC'16 abstract model as a lane env (gym/rust/src/fc16.rs FC16SSZwPT,
+    CPR_PROTO_FC16_ENV) for ``envs.device_env_fn``: not a protocol of the reference's engine.
+    Observations are x / (1 + x) of (a, h, fork) whatever ``unit_observation`` says."""
+    horizon = float(horizon)
+    if not horizon >= 1:
+        raise ValueError("horizon must be >= 1")
+    return Protocol("fc16", "FC'16 abstract selfish-mining model with probabilistic termination",
+                    "index into [Wait, Adopt, Override if a > h, Match if a >= h]",
+                    unit_observation, protocol_id=L.PROTO_FC16_ENV, horizon=horizon)

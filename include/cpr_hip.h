@@ -60,10 +60,22 @@ enum cpr_protocol {
   CPR_PROTO_BK = 2,       /* bk.ml + bk_ssz.ml (cpr_protocols.ml:53-72), k = cpr_config.k */
   CPR_PROTO_TAILSTORM = 3, /* tailstorm.ml + tailstorm_ssz.ml (cpr_protocols.ml:153-175),
                              k = cpr_config.k, selection = cpr_config.subblock_selection */
-  CPR_PROTO_FC16 = 4       /* the FC'16 abstract selfish-mining model with probabilistic
+  CPR_PROTO_FC16 = 4,      /* the FC'16 abstract selfish-mining model with probabilistic
                              termination, gym/rust/src/fc16.rs FC16SSZwPT: alpha, gamma,
                              horizon, policy = enum cpr_fc16_policy; fused episodes only
                              (cpr_run_episodes); max_steps caps an episode (CPR_ST_CAPACITY) */
+  CPR_PROTO_FC16_ENV = 5   /* the same model as a lockstep env (additive within ABI v11; a new
+                             id because CPR_PROTO_FC16 keeps refusing every lockstep entry).
+                             cpr_run_episodes as CPR_PROTO_FC16, and with n_lanes > 0:
+                             cpr_reset / cpr_step (action = index 0..3 into the offered list
+                             [Wait, Adopt, Override if a > h, Match if a >= h], an index beyond
+                             the list acts as Wait, fc16.rs:49-60,182; observation x / (1 + x)
+                             of (a, h, fork), unit_observation ignored; done = terminated, or
+                             max_steps steps: CPR_ST_CAPACITY), cpr_observe_fields (a, h, fork),
+                             the policy network, cpr_rollout_net(_env), the lane env, the
+                             learner and cpr_eval_net. CPR_E_UNSUPPORTED: cpr_rollout,
+                             cpr_policy_actions, cpr_replay, cpr_node_outputs and
+                             CPR_GYM_REWARD_DENSE_PER_PROGRESS (no progress target) */
 };
 
 /* policies of the FC16 model (fc16_lane.h); a table maps (a, h, fork) to an action name
@@ -641,6 +653,14 @@ typedef struct cpr_rollout_env_out {
 int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
                         const cpr_rollout_net_out* out, const cpr_rollout_env_out* env_out,
                         int outputs_on_device, cpr_summary* summary);
+/* Whether the batch's last cpr_rollout_net / _env (cpr_ppo_iterate's included) ran its steps in
+ * one kernel (added within v11). CPR_PROTO_FC16_ENV batches do when the environment variable
+ * CPR_FC16_ROLLOUT_FUSED=1 is set (read at every call) and the kernel's LDS fits the device,
+ * with the same outputs bit for bit as the launch sequence that every protocol runs by default
+ * (CPR_FC16_ROLLOUT_FUSED=0 or unset): forward, step, collect and reset kernels per step. The
+ * one-kernel path is faster at a few thousand lanes and slower at 65,536 lanes with a 3 x 64
+ * network, hence off by default. */
+int cpr_rollout_net_fused(cpr_batch* b, int32_t* fused);
 
 /* A cyclic assumption schedule (added within v11; a batch that never calls this launches what
  * it did before). CPR_SCHEDULE_CHOICE is the keyed random.choice above. Under

@@ -26,6 +26,7 @@ let proto_ethereum = 1l
 let proto_bk = 2l
 let proto_tailstorm = 3l
 let proto_fc16 = 4l
+let proto_fc16_env = 5l (* the same model with lockstep lanes (added within ABI v11) *)
 let net_selfish_mining = 0l
 let net_two_agents = 1l
 let net_honest_clique = 2l
@@ -270,6 +271,11 @@ let rollout_net_env =
     "cpr_rollout_net_env"
     (ptr batch @-> int64_t @-> int @-> ptr void @-> ptr void @-> int @-> ptr summary
     @-> returning int)
+;;
+
+(* whether the last network rollout ran as one kernel (FC16 env batches; added within v11) *)
+let rollout_net_fused =
+  foreign "cpr_rollout_net_fused" (ptr batch @-> ptr int32_t @-> returning int)
 ;;
 
 (* the learner (added within ABI v11): cpr_ppo_opts, cpr_ppo_data and cpr_ppo_stats are

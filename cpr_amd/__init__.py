@@ -9,6 +9,7 @@ Layout (DESIGN.md):
   envs.py      Core env, env_fn and registered ids (gym/ocaml/cpr_gym/envs.py)
   wrappers.py  reward / assumption wrappers (gym/ocaml/cpr_gym/wrappers.py)
   ppo.py       the learner's options, flat parameter order and training loop (cpr_ppo_*)
+  dqn.py       Q-learning's options, presets, schedules and training loop (cpr_dqn_*)
   parallel.py  one process per GPU, episode sharding, RCCL all-reduce of batch summaries
 """
 

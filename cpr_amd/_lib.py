@@ -415,6 +415,58 @@ class PpoStats(ctypes.Structure):
 
 
 TAG_PERM = 0x80000000  # keyed-stream tag of cpr_ppo_update's permutations
+TAG_EXPLORE = 0x90000000  # ... of cpr_dqn_collect's exploration coins (dqn.h)
+TAG_REPLAY = 0xA0000000  # ... of cpr_dqn_update's sampled transitions
+
+
+class DqnOptsC(ctypes.Structure):
+    """cpr_dqn_opts (include/cpr_hip.h)."""
+
+    _fields_ = [
+        ("batch", ctypes.c_int64),
+        ("gradient_steps", ctypes.c_int32),
+        ("gamma", ctypes.c_double),
+        ("lr", ctypes.c_double),
+        ("beta1", ctypes.c_double),
+        ("beta2", ctypes.c_double),
+        ("adam_eps", ctypes.c_double),
+        ("max_grad_norm", ctypes.c_double),
+        ("tau", ctypes.c_double),
+        ("target_update_interval", ctypes.c_int64),
+        ("learning_starts", ctypes.c_int64),
+        ("sample_seed", ctypes.c_uint64),
+    ]
+
+
+class DqnDataC(ctypes.Structure):
+    """cpr_dqn_data: n transitions, host or device pointers."""
+
+    _fields_ = [
+        ("n", ctypes.c_int64),
+        ("obs", ctypes.c_void_p),
+        ("alpha", ctypes.c_void_p),
+        ("action", ctypes.c_void_p),
+        ("reward", ctypes.c_void_p),
+        ("done", ctypes.c_void_p),
+        ("next_obs", ctypes.c_void_p),
+        ("on_device", ctypes.c_int32),
+    ]
+
+
+class DqnStats(ctypes.Structure):
+    """cpr_dqn_stats: the statistics of a gradient step or an update."""
+
+    _fields_ = [
+        ("loss", ctypes.c_double),
+        ("abs_td", ctypes.c_double),
+        ("q", ctypes.c_double),
+        ("target", ctypes.c_double),
+        ("grad_norm", ctypes.c_double),
+        ("n_steps", ctypes.c_int64),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class CTrace(ctypes.Structure):
@@ -547,6 +599,17 @@ EXPORTS = [
     "cpr_ppo_param_count",
     "cpr_ppo_update",
     "cpr_ppo_iterate",
+    "cpr_dqn_opts_default",
+    "cpr_dqn_init",
+    "cpr_dqn_collect",
+    "cpr_dqn_gradients",
+    "cpr_dqn_update",
+    "cpr_dqn_last_indices",
+    "cpr_dqn_target_sync",
+    "cpr_dqn_iterate",
+    "cpr_dqn_replay_get",
+    "cpr_dqn_replay_state",
+    "cpr_dqn_target_get",
     "cpr_policy_net_get",
     "cpr_policy_actions",
     "cpr_observation_spec",
@@ -612,6 +675,20 @@ def _declare(L):
     L.cpr_ppo_param_count.argtypes = [vp, P(ctypes.c_int64)]
     L.cpr_ppo_update.argtypes = [vp, P(PpoDataC), P(PpoOptsC), vp, P(PpoStats)]
     L.cpr_ppo_iterate.argtypes = [vp, ctypes.c_int64, P(PpoOptsC), P(Summary), P(PpoStats)]
+    L.cpr_dqn_opts_default.argtypes = [P(DqnOptsC)]
+    L.cpr_dqn_init.argtypes = [vp, ctypes.c_int64]
+    L.cpr_dqn_collect.argtypes = [vp, ctypes.c_int64, ctypes.c_double, P(Summary)]
+    L.cpr_dqn_gradients.argtypes = [vp, P(DqnDataC), vp, ctypes.c_int64, P(DqnOptsC), vp,
+                                    P(DqnStats)]
+    L.cpr_dqn_update.argtypes = [vp, ctypes.c_int32, P(DqnOptsC), vp, P(DqnStats)]
+    L.cpr_dqn_last_indices.argtypes = [vp, vp, ctypes.c_int64]
+    L.cpr_dqn_target_sync.argtypes = [vp, ctypes.c_double]
+    L.cpr_dqn_iterate.argtypes = [vp, ctypes.c_int64, ctypes.c_double, P(DqnOptsC), P(Summary),
+                                  P(DqnStats)]
+    L.cpr_dqn_replay_get.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, P(DqnDataC)]
+    L.cpr_dqn_replay_state.argtypes = [vp, P(ctypes.c_int64), P(ctypes.c_int64),
+                                       P(ctypes.c_int64)]
+    L.cpr_dqn_target_get.argtypes = [vp, P(PolicyNetC)]
     L.cpr_policy_net_get.argtypes = [vp, P(PolicyNetC)]
     L.cpr_policy_actions.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int64, vp]
     L.cpr_observation_spec.argtypes = [vp, P(ctypes.c_int32), P(ctypes.c_int32), vp, vp]

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/cpr_hip.h"
+#include "dqn.h"
 #include "eth_window.h"
 #include "kernels.h"
 #include "lane_env.h"
@@ -238,6 +239,18 @@ struct cpr_batch {
   DevBuf pp_obs, pp_alpha, pp_action, pp_logp, pp_adv, pp_ret;
   std::vector<int32_t> perm_host;
   DevBuf it_obs, it_alpha, it_action, it_reward, it_done, it_logp, it_value, it_adv, it_ret;
+  // Q-learning (cpr_dqn_*): the replay ring of dq_cap slots (and a guard slot) of n_lanes
+  // transitions as structure of arrays, its cursor and size in slots, the vector steps
+  // collected and the updates run since cpr_dqn_init; the target network (dq_tn: pn over
+  // dq_tw); the gradient (its vf part stays zero), the indices of the last update; staging of
+  // cpr_dqn_gradients' host data
+  bool dq_ready = false;
+  int64_t dq_cap = 0, dq_cursor = 0, dq_size = 0, dq_steps = 0, dq_updates = 0;
+  PolNet dq_tn;
+  DevBuf dq_tw, dq_obs, dq_next, dq_alpha, dq_action, dq_reward, dq_done, dq_grad, dq_idx;
+  int64_t dq_idx_n = 0;
+  std::vector<int64_t> dq_idx_host;
+  DevBuf ds_obs, ds_next, ds_alpha, ds_action, ds_reward, ds_done, ds_idx;
   bool reset_done = false;
   int32_t tab_n = 4096;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -2663,6 +2676,29 @@ int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint
 
 // ---------------------------------------------------------------- neural-network policies
 
+// Q-learning's view of a new network b->pn (cpr_dqn_init, cpr_policy_net_set / _copy on a batch
+// with a ring): the target becomes a copy of the weights in the same padded layout, the
+// gradient buffer is zero (its vf part stays so), the update count starts over
+static int dqn_target_reset(cpr_batch* b) {
+  hipStream_t st = b->ctx->stream;
+  const size_t bytes = (size_t)b->pn_total * sizeof(float);
+  HIP_TRY(hipStreamSynchronize(st));  // a kernel may still be reading the previous buffers
+  HIP_TRY(b->dq_tw.ensure(bytes));
+  HIP_TRY(b->dq_grad.ensure(bytes));
+  HIP_TRY(hipMemcpyAsync(b->dq_tw.p, b->pn_w.p, bytes, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemsetAsync(b->dq_grad.p, 0, b->dq_grad.bytes, st));
+  b->dq_tn = b->pn;
+  const float* from = (const float*)b->pn_w.p;
+  const float* to = (const float*)b->dq_tw.p;
+  for (PolLayer* Ls : {b->dq_tn.pi, b->dq_tn.vf})
+    for (int l = 0; l <= b->pn.depth; l++) {
+      Ls[l].W = to + (Ls[l].W - from);
+      Ls[l].b = to + (Ls[l].b - from);
+    }
+  b->dq_updates = 0;
+  return CPR_OK;
+}
+
 int cpr_policy_net_set(cpr_batch* b, const cpr_policy_net* net) {
   if (!b || !net) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
@@ -2757,6 +2793,7 @@ int cpr_policy_net_set(cpr_batch* b, const cpr_policy_net* net) {
   b->pp_part.release();  // its zeroed padding stood where the previous network's was
   b->pn = N;
   b->has_net = true;
+  if (b->dq_ready) return dqn_target_reset(b);
   return CPR_OK;
 }
 
@@ -2908,9 +2945,36 @@ int cpr_rollout_net(cpr_batch* b, int64_t n_steps, int deterministic,
   return cpr_rollout_net_env(b, n_steps, deterministic, out, nullptr, outputs_on_device, summary);
 }
 
+// slot `slot` of the replay ring
+static DqnRows dqn_slot(const cpr_batch* b, int64_t slot) {
+  const size_t r = (size_t)slot * (size_t)b->cfg.n_lanes, ol = (size_t)b->pn.obs_len;
+  DqnRows S;
+  S.obs = (float*)b->dq_obs.p + r * ol;
+  S.next_obs = (float*)b->dq_next.p + r * ol;
+  S.alpha = (double*)b->dq_alpha.p + r;
+  S.action = (int32_t*)b->dq_action.p + r;
+  S.reward = (double*)b->dq_reward.p + r;
+  S.done = (uint8_t*)b->dq_done.p + r;
+  return S;
+}
+
+static int rollout_net_run(cpr_batch* b, int64_t n_steps, int deterministic,
+                           const cpr_rollout_net_out* out, const cpr_rollout_env_out* env_out,
+                           int outputs_on_device, cpr_summary* summary, const double* dqn_epsilon);
+
 int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
                         const cpr_rollout_net_out* out, const cpr_rollout_env_out* env_out,
                         int outputs_on_device, cpr_summary* summary) {
+  return rollout_net_run(b, n_steps, deterministic, out, env_out, outputs_on_device, summary,
+                         nullptr);
+}
+
+// cpr_rollout_net_env, and with dqn_epsilon cpr_dqn_collect: the same launch sequence with the
+// epsilon-greedy forward (k_dqn_act) in k_policy_forward's place, no step-major outputs, and
+// step t's transitions written to slot (cursor + t) mod capacity of the replay ring
+static int rollout_net_run(cpr_batch* b, int64_t n_steps, int deterministic,
+                           const cpr_rollout_net_out* out, const cpr_rollout_env_out* env_out,
+                           int outputs_on_device, cpr_summary* summary, const double* dqn_epsilon) {
   if (!b || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
   if (b->cfg.protocol == CPR_PROTO_FC16)
@@ -3034,7 +3098,7 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
 #endif
   const char* fv = getenv("CPR_FC16_ROLLOUT_FUSED");
   const bool want_fused = fv ? fv[0] != '0' : CPR_FC16_ROLLOUT_FUSED_DEFAULT != 0;
-  const bool fused = b->fc16_env && want_fused && fc16_rollout_net_fits(b->pn);
+  const bool fused = !dqn_epsilon && b->fc16_env && want_fused && fc16_rollout_net_fits(b->pn);
   b->roll_fused = fused;
   if (fused) {
     Fc16Roll R = {};
@@ -3075,21 +3139,40 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
   const double* in_obs = sb.obs;
   for (int64_t t = 0; t < n_steps && !fused; ++t) {
     int32_t* act = D.action ? D.action + t * n : (int32_t*)b->l_act.p;
-    io.obs = in_obs;
-    io.action = act;
-    io.logp = D.logp ? D.logp + t * n : nullptr;
-    io.value = D.value ? D.value + t * n : nullptr;
-    HIP_TRY(launch_policy_forward(b->pn, io, st));
+    DqnRows slot = {};
+    if (dqn_epsilon) {
+      slot = dqn_slot(b, (b->dq_cursor + t) % b->dq_cap);
+      DqnAct A = {};
+      A.obs = in_obs;
+      A.n = n;
+      A.epsilon = *dqn_epsilon;
+      A.seed = b->cfg.seed;
+      A.ep = cur.ep;
+      A.step = cur.steps;
+      A.lane_alpha = env ? (const double*)b->le_lane_a.p : nullptr;
+      A.alpha_col = io.alpha_col;
+      A.cfg_alpha = b->cfg.alpha;
+      A.action = act;
+      A.slot = slot;
+      HIP_TRY(launch_dqn_act(b->pn, A, st));
+    } else {
+      io.obs = in_obs;
+      io.action = act;
+      io.logp = D.logp ? D.logp + t * n : nullptr;
+      io.value = D.value ? D.value + t * n : nullptr;
+      HIP_TRY(launch_policy_forward(b->pn, io, st));
+    }
     rc = launch_lock_step(b, act, sb);
     if (rc) return rc;
-    C.out_reward = D.reward ? D.reward + t * n : nullptr;
-    C.out_done = D.done ? D.done + t * n : nullptr;
+    C.out_reward = dqn_epsilon ? slot.reward : D.reward ? D.reward + t * n : nullptr;
+    C.out_done = dqn_epsilon ? slot.done : D.done ? D.done + t * n : nullptr;
     C.out_engine_reward = DE.engine_reward ? DE.engine_reward + t * n : nullptr;
     HIP_TRY(launch_policy_collect(C, n, st));
     double* next_obs = D.obs ? D.obs + t * n * ol : sb.obs;
     rc = launch_lock_reset(b, C.mask, cur.ep, next_obs,
                            env && DE.alpha ? DE.alpha + t * n : nullptr);
     if (rc) return rc;
+    if (dqn_epsilon) HIP_TRY(launch_dqn_store(next_obs, n * ol, slot.next_obs, st));
     in_obs = next_obs;
   }
   if (D.value && !fused) {  // PPO's bootstrap: the value of the final observation
@@ -3122,6 +3205,11 @@ int cpr_rollout_net_env(cpr_batch* b, int64_t n_steps, int deterministic,
   b->reset_done = true;
   b->last_lanes = n;
   b->last_resident = n;
+  if (dqn_epsilon) {
+    b->dq_cursor = (b->dq_cursor + n_steps) % b->dq_cap;
+    b->dq_size = std::min(b->dq_cap, b->dq_size + n_steps);
+    b->dq_steps += n_steps;
+  }
   summary->episodes += s.episodes;
   summary->steps += s.steps;
   summary->activations += s.activations;
@@ -3407,6 +3495,7 @@ int cpr_policy_net_copy(cpr_batch* dst, cpr_batch* src) {
   if (!dst->has_net) dst->pp_part.release();
   dst->pn = N;
   dst->has_net = true;
+  if (dst->dq_ready) return dqn_target_reset(dst);
   return CPR_OK;
 }
 
@@ -3611,6 +3700,19 @@ static int ppo_scratch(cpr_batch* b, int64_t B) {
   return CPR_OK;
 }
 
+// what a training forward leaves for the backward: the f32 input rows, each trunk's saved
+// activations and the loss's derivative at the heads. pi_only (Q-learning): the vf trunk's
+// jobs are empty and only the pi part of `grad` is written
+struct PpoBack {
+  const float* xin;
+  float* const* act[2];
+  const float* dlogits;
+  const float* dvalue;
+  bool pi_only;
+  float* grad;
+};
+static int ppo_backward(cpr_batch* b, int64_t B, const PpoBack& K, double* acc);
+
 // the gradient of minibatch idx[0 .. B) into pp_grad and its statistics into pp_stats (added
 // to acc if given); launches only
 static int ppo_minibatch(cpr_batch* b, const PpoDev& D, const int32_t* idx, int64_t B,
@@ -3647,7 +3749,23 @@ static int ppo_minibatch(cpr_batch* b, const PpoDev& D, const int32_t* idx, int6
   HIP_TRY(launch_ppo_forward(N, F, st));
   const int64_t blocks = (B + kPolRows - 1) / kPolRows;
   HIP_TRY(launch_ppo_stats(F.partial, blocks, B, o.ent_coef, o.vf_coef, stats, acc, st));
-  // backward, from each head down; both trunks' layer l in one launch
+  PpoBack K = {};
+  K.xin = F.xin;
+  K.act[0] = F.act[0];
+  K.act[1] = F.act[1];
+  K.dlogits = F.dlogits;
+  K.dvalue = F.dvalue;
+  K.grad = (float*)b->pp_grad.p;
+  return ppo_backward(b, B, K, acc);
+}
+
+// backward from each head down (both trunks' layer l in one launch), the row blocks'
+// partials summed into K.grad, and its norm into pp_stats (added to acc if given)
+static int ppo_backward(cpr_batch* b, int64_t B, const PpoBack& K, double* acc) {
+  const PolNet& N = b->pn;
+  hipStream_t st = b->ctx->stream;
+  double* stats = (double*)b->pp_stats.p;
+  double* red = (double*)b->pp_red.p;
   PpoBwd P = {};
   P.B = B;
   P.rows_per_block = ppo_rows_per_block(B);
@@ -3664,16 +3782,17 @@ static int ppo_minibatch(cpr_batch* b, const PpoDev& D, const int32_t* idx, int6
   P.bstride = M.start[M.arrays];
   const size_t wmax = (size_t)std::max(N.width_pi, N.width_vf);
   float* dy[2] = {(float*)b->pp_dy0.p, (float*)b->pp_dy1.p};
-  const float* cur[2] = {F.dlogits, F.dvalue};
+  const float* cur[2] = {K.dlogits, K.dvalue};
   int32_t ld[2] = {N.n_actions, 1};
+  const int trunks = K.pi_only ? 1 : 2;  // P.j[1] stays empty: no tile, no dX
   for (int l = N.depth; l >= 0; l--) {
     float* out = dy[(N.depth - l) & 1];
-    for (int trunk = 0; trunk < 2; trunk++) {
+    for (int trunk = 0; trunk < trunks; trunk++) {
       const PolLayer& Ly = trunk == 0 ? N.pi[l] : N.vf[l];
       PpoBwdJob& J = P.j[trunk];
       J.dY = cur[trunk];
       J.ldy = ld[trunk];
-      J.X = l == 0 ? F.xin : F.act[trunk][l - 1];
+      J.X = l == 0 ? K.xin : K.act[trunk][l - 1];
       J.ldx = l == 0 ? kPolInStride : Ly.n_in;
       J.W = Ly.W;
       J.n_out = Ly.n_out;
@@ -3687,17 +3806,19 @@ static int ppo_minibatch(cpr_batch* b, const PpoDev& D, const int32_t* idx, int6
     HIP_TRY(launch_ppo_dw(P, st));
     if (l > 0) {
       HIP_TRY(launch_ppo_dx(P, st));
-      for (int trunk = 0; trunk < 2; trunk++) {
+      for (int trunk = 0; trunk < trunks; trunk++) {
         cur[trunk] = P.j[trunk].dX;
         ld[trunk] = P.j[trunk].n_in;
       }
     }
   }
   const int32_t rb = (int32_t)((B + P.rows_per_block - 1) / P.rows_per_block);
-  HIP_TRY(launch_ppo_reduce(P.part, P.pstride, rb, b->pn_total, (float*)b->pp_grad.p, st));
-  HIP_TRY(launch_ppo_reduce_bias(P.bpart, P.bstride, rb, M, (float*)b->pp_grad.p, st));
-  HIP_TRY(launch_grad_norm((const float*)b->pp_grad.p, b->pn_total, red + 2 * kPpoRedBlocks, stats,
-                           acc, st));
+  // the pi trunk's arrays stand first in the layout
+  const int64_t n_red = K.pi_only ? b->pn_off[(size_t)2 * (N.depth + 1)] : b->pn_total;
+  if (K.pi_only) M.arrays = N.depth + 1;
+  HIP_TRY(launch_ppo_reduce(P.part, P.pstride, rb, n_red, K.grad, st));
+  HIP_TRY(launch_ppo_reduce_bias(P.bpart, P.bstride, rb, M, K.grad, st));
+  HIP_TRY(launch_grad_norm(K.grad, b->pn_total, red + 2 * kPpoRedBlocks, stats, acc, st));
   return CPR_OK;
 }
 
@@ -3901,10 +4022,434 @@ int cpr_ppo_iterate(cpr_batch* b, int64_t n_steps, const cpr_ppo_opts* opts,
   return cpr_ppo_update(b, &d, opts, nullptr, stats_out);
 }
 
+// ---------------------------------------------------------------- Q-learning (dqn.h)
+
+int cpr_dqn_opts_default(cpr_dqn_opts* o) {
+  if (!o) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  *o = cpr_dqn_opts{};
+  o->batch = 32;
+  o->gradient_steps = 1;
+  o->gamma = 0.99;
+  o->lr = 1e-4;
+  o->beta1 = 0.9;
+  o->beta2 = 0.999;
+  o->adam_eps = 1e-8;
+  o->max_grad_norm = 10.0;
+  o->tau = 1.0;
+  o->target_update_interval = 10000;
+  o->learning_starts = 50000;
+  o->sample_seed = 0;
+  return CPR_OK;
+}
+
+// the batch can hold a Q-network at all, and holds one (and a ring, if asked for)
+static int dqn_state(cpr_batch* b, bool need_ring) {
+  if (!b) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (b->cfg.protocol == CPR_PROTO_FC16)
+    return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
+  if (b->cfg.n_lanes <= 0 || b->cfg.mode != CPR_MODE_GYM)
+    return fail(CPR_E_UNSUPPORTED, "Q-learning needs lockstep lanes (CPR_MODE_GYM, "
+                                   "cfg.n_lanes > 0)");
+  if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
+  if (need_ring && !b->dq_ready) return fail(CPR_E_STATE, "no replay ring (cpr_dqn_init)");
+  return CPR_OK;
+}
+
+// state, shapes and options of the cpr_dqn_* calls that take options, before any launch
+static int dqn_check(cpr_batch* b, const cpr_dqn_opts* o) {
+  int rc = dqn_state(b, true);
+  if (rc) return rc;
+  if (!o) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (o->batch < 1) return fail(CPR_E_INVALID_ARG, "dqn: batch must be >= 1");
+  if (o->batch > INT32_MAX) return fail(CPR_E_INVALID_ARG, "dqn: batch above 2^31 - 1");
+  if (o->gradient_steps < 0) return fail(CPR_E_INVALID_ARG, "dqn: gradient_steps must be >= 0");
+  if (o->target_update_interval < 1)
+    return fail(CPR_E_INVALID_ARG, "dqn: target_update_interval must be >= 1");
+  if (o->learning_starts < 0) return fail(CPR_E_INVALID_ARG, "dqn: learning_starts must be >= 0");
+  const struct {
+    const char* name;
+    double v;
+    bool positive;
+  } fields[] = {{"gamma", o->gamma, false},       {"lr", o->lr, false},
+                {"beta1", o->beta1, false},       {"beta2", o->beta2, false},
+                {"adam_eps", o->adam_eps, false}, {"max_grad_norm", o->max_grad_norm, true},
+                {"tau", o->tau, false}};
+  for (const auto& f : fields) {
+    if (!std::isfinite(f.v)) return fail(CPR_E_INVALID_ARG, std::string("dqn: non-finite ") + f.name);
+    if (f.positive && !(f.v > 0.0))
+      return fail(CPR_E_INVALID_ARG, std::string("dqn: ") + f.name + " must be > 0");
+  }
+  if (!(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0))
+    return fail(CPR_E_INVALID_ARG, "dqn: beta1 and beta2 must be in [0, 1)");
+  if (!(o->tau >= 0.0 && o->tau <= 1.0)) return fail(CPR_E_INVALID_ARG, "dqn: tau must be in [0, 1]");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  const int64_t lds = policy_lds_bytes(b->pn.depth, b->pn.width_pi, b->pn.width_vf);
+  if (lds > dqn_lds_limit())
+    return fail(CPR_E_UNSUPPORTED,
+                "dqn: the forward of this network needs " + std::to_string(lds) +
+                    " B of LDS per workgroup, the device has " + std::to_string(dqn_lds_limit()));
+  return CPR_OK;
+}
+
+int cpr_dqn_init(cpr_batch* b, int64_t capacity_steps) {
+  int rc = dqn_state(b, false);
+  if (rc) return rc;
+  CPR_ENTER(b->ctx);
+  if (capacity_steps < 1) return fail(CPR_E_INVALID_ARG, "dqn: capacity_steps must be >= 1");
+  const int64_t n = b->cfg.n_lanes;
+  if (capacity_steps > (INT64_MAX >> 8) / n)
+    return fail(CPR_E_INVALID_ARG, "dqn: capacity_steps * n_lanes overflows");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  hipStream_t st = b->ctx->stream;
+  HIP_TRY(hipStreamSynchronize(st));  // a kernel may still be reading a previous ring
+  b->dq_ready = false;
+  // the ring and its guard slot; a failed allocation leaves the batch without a ring
+  const size_t rows = (size_t)(capacity_steps + 1) * (size_t)n, ol = (size_t)b->pn.obs_len;
+  struct {
+    DevBuf* buf;
+    size_t bytes;
+  } arrs[] = {{&b->dq_obs, rows * ol * 4}, {&b->dq_next, rows * ol * 4}, {&b->dq_alpha, rows * 8},
+              {&b->dq_action, rows * 4},   {&b->dq_reward, rows * 8},    {&b->dq_done, rows}};
+  for (auto& a : arrs) {
+    a.buf->release();
+    HIP_TRY(a.buf->ensure(a.bytes));
+  }
+  for (auto& a : arrs) {
+    const size_t ring = a.bytes / (size_t)(capacity_steps + 1) * (size_t)capacity_steps;
+    HIP_TRY(hipMemsetAsync(a.buf->p, 0, ring, st));
+    HIP_TRY(hipMemsetAsync((char*)a.buf->p + ring, 0xA5, a.bytes - ring, st));
+  }
+  b->dq_cap = capacity_steps;
+  b->dq_cursor = 0;
+  b->dq_size = 0;
+  b->dq_steps = 0;
+  b->dq_idx_n = 0;
+  b->ppo_t = 0;
+  if (b->pp_m.p) HIP_TRY(hipMemsetAsync(b->pp_m.p, 0, b->pp_m.bytes, st));
+  if (b->pp_v.p) HIP_TRY(hipMemsetAsync(b->pp_v.p, 0, b->pp_v.bytes, st));
+  rc = dqn_target_reset(b);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  b->dq_ready = true;
+  return CPR_OK;
+}
+
+int cpr_dqn_collect(cpr_batch* b, int64_t n_steps, double epsilon, cpr_summary* summary) {
+  int rc = dqn_state(b, true);
+  if (rc) return rc;
+  if (!(epsilon >= 0.0 && epsilon <= 1.0))
+    return fail(CPR_E_INVALID_ARG, "dqn: epsilon must be in [0, 1]");
+  if (n_steps < 0) return fail(CPR_E_INVALID_ARG, "dqn: n_steps must be >= 0");
+  return rollout_net_run(b, n_steps, 1, nullptr, nullptr, 1, summary, &epsilon);
+}
+
+int cpr_dqn_replay_state(cpr_batch* b, int64_t* size, int64_t* cursor, int64_t* capacity) {
+  int rc = dqn_state(b, true);
+  if (rc) return rc;
+  if (size) *size = b->dq_size;
+  if (cursor) *cursor = b->dq_cursor;
+  if (capacity) *capacity = b->dq_cap;
+  return CPR_OK;
+}
+
+int cpr_dqn_replay_get(cpr_batch* b, int64_t first_slot, int64_t n_slots, cpr_dqn_data* out) {
+  int rc = dqn_state(b, true);
+  if (rc) return rc;
+  CPR_ENTER(b->ctx);
+  if (!out || !out->obs || !out->action || !out->reward || !out->done || !out->next_obs)
+    return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (first_slot < 0 || n_slots < 1 || first_slot > b->dq_cap || n_slots > b->dq_cap + 1 - first_slot)
+    return fail(CPR_E_INVALID_ARG, "dqn: slots outside the ring and its guard slot");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  hipStream_t st = b->ctx->stream;
+  const size_t rows = (size_t)n_slots * (size_t)b->cfg.n_lanes, ol = (size_t)b->pn.obs_len;
+  const DqnRows S = dqn_slot(b, first_slot);
+  std::vector<float> o32(rows * ol), n32(rows * ol);
+  HIP_TRY(hipMemcpyAsync(o32.data(), S.obs, rows * ol * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(n32.data(), S.next_obs, rows * ol * 4, hipMemcpyDeviceToHost, st));
+  if (out->alpha)
+    HIP_TRY(hipMemcpyAsync((void*)out->alpha, S.alpha, rows * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync((void*)out->action, S.action, rows * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync((void*)out->reward, S.reward, rows * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync((void*)out->done, S.done, rows, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (size_t i = 0; i < rows * ol; i++) {
+    ((double*)out->obs)[i] = (double)o32[i];
+    ((double*)out->next_obs)[i] = (double)n32[i];
+  }
+  out->n = (int64_t)rows;
+  out->on_device = 0;
+  return CPR_OK;
+}
+
+static int policy_net_read(cpr_batch* b, const void* weights, cpr_policy_net* net);
+
+int cpr_dqn_target_get(cpr_batch* b, cpr_policy_net* net) {
+  int rc = dqn_state(b, true);
+  if (rc) return rc;
+  if (!net) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(b->ctx);
+  return policy_net_read(b, b->dq_tw.p, net);
+}
+
+// the gradient of the transitions idx[0 .. B) of F's rows into dq_grad and the step's
+// statistics into pp_stats (added to acc if given); launches only
+static int dqn_minibatch(cpr_batch* b, DqnFwd F, const int64_t* idx, int64_t B, double* acc) {
+  const PolNet& N = b->pn;
+  hipStream_t st = b->ctx->stream;
+  F.idx = idx;
+  F.B = B;
+  F.xin = (float*)b->pp_xin.p;
+  float* ap = (float*)b->pp_act.p;
+  for (int l = 0; l < N.depth; l++) {
+    F.act[l] = ap;
+    ap += (size_t)B * (size_t)N.width_pi;
+  }
+  F.dlogits = (float*)b->pp_dlg.p;
+  F.partial = (double*)b->pp_partial.p;
+  HIP_TRY(launch_dqn_forward(N, b->dq_tn, F, st));
+  const int64_t blocks = (B + kPolRows - 1) / kPolRows;
+  HIP_TRY(launch_dqn_stats(F.partial, blocks, B, (double*)b->pp_stats.p, acc, st));
+  PpoBack K = {};
+  K.xin = F.xin;
+  K.act[0] = F.act;
+  K.dlogits = F.dlogits;
+  K.pi_only = true;
+  K.grad = (float*)b->dq_grad.p;
+  return ppo_backward(b, B, K, acc);
+}
+
+static void dqn_stats_out(const double* s, double div, int64_t count, cpr_dqn_stats* out) {
+  out->loss = s[kDqnLoss] / div;
+  out->abs_td = s[kDqnAbsTd] / div;
+  out->q = s[kDqnQ] / div;
+  out->target = s[kDqnTarget] / div;
+  out->grad_norm = s[kPpoGradNorm] / div;
+  out->n_steps = count;
+}
+
+int cpr_dqn_gradients(cpr_batch* b, const cpr_dqn_data* data, const int64_t* rows_idx,
+                      int64_t n_rows, const cpr_dqn_opts* opts, float* grad_out,
+                      cpr_dqn_stats* stats_out) {
+  int rc = dqn_check(b, opts);
+  if (rc) return rc;
+  CPR_ENTER(b->ctx);
+  if (!data || !rows_idx || !grad_out) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (n_rows < 1 || n_rows > INT32_MAX)
+    return fail(CPR_E_INVALID_ARG, "dqn: n_rows must be in 1 .. 2^31 - 1");
+  if (data->n < 1) return fail(CPR_E_INVALID_ARG, "dqn: data.n must be >= 1");
+  if (!data->obs || !data->action || !data->reward || !data->done || !data->next_obs)
+    return fail(CPR_E_INVALID_ARG, "dqn: NULL data array");
+  const bool use_alpha = b->has_env && b->env.alpha_column >= 0;
+  if (use_alpha && !data->alpha)
+    return fail(CPR_E_INVALID_ARG, "dqn: data.alpha is NULL but the lane env names an alpha column");
+  hipStream_t st = b->ctx->stream;
+  DqnFwd F = {};
+  F.N = data->n;
+  F.gamma = opts->gamma;
+  F.alpha_col = use_alpha ? b->env.alpha_column : -1;
+  const int64_t* idx = rows_idx;
+  if (data->on_device) {
+    F.obs64 = data->obs;
+    F.next64 = data->next_obs;
+    F.alpha = use_alpha ? data->alpha : nullptr;
+    F.action = data->action;
+    F.reward = data->reward;
+    F.done = data->done;
+  } else {
+    const size_t n = (size_t)data->n, ol = (size_t)b->pn.obs_len;
+    for (size_t i = 0; i < n; i++)
+      if (data->action[i] < 0 || data->action[i] >= b->pn.n_actions)
+        return fail(CPR_E_INVALID_ARG, "dqn: data.action out of range");
+    for (int64_t i = 0; i < n_rows; i++)
+      if (rows_idx[i] < 0 || rows_idx[i] >= data->n)
+        return fail(CPR_E_INVALID_ARG, "dqn: rows_idx out of range");
+    struct {
+      DevBuf* buf;
+      const void* src;
+      size_t bytes;
+    } cp[] = {{&b->ds_obs, data->obs, n * ol * 8},
+              {&b->ds_next, data->next_obs, n * ol * 8},
+              {&b->ds_alpha, use_alpha ? data->alpha : nullptr, n * 8},
+              {&b->ds_action, data->action, n * 4},
+              {&b->ds_reward, data->reward, n * 8},
+              {&b->ds_done, data->done, n},
+              {&b->ds_idx, rows_idx, (size_t)n_rows * 8}};
+    for (auto& c : cp) {
+      if (!c.src) continue;
+      HIP_TRY(c.buf->ensure(c.bytes));
+      HIP_TRY(hipMemcpyAsync(c.buf->p, c.src, c.bytes, hipMemcpyHostToDevice, st));
+    }
+    F.obs64 = (const double*)b->ds_obs.p;
+    F.next64 = (const double*)b->ds_next.p;
+    F.alpha = use_alpha ? (const double*)b->ds_alpha.p : nullptr;
+    F.action = (const int32_t*)b->ds_action.p;
+    F.reward = (const double*)b->ds_reward.p;
+    F.done = (const uint8_t*)b->ds_done.p;
+    idx = (const int64_t*)b->ds_idx.p;
+  }
+  rc = ppo_scratch(b, n_rows);
+  if (rc) return rc;
+  rc = dqn_minibatch(b, F, idx, n_rows, nullptr);
+  if (rc) return rc;
+  float* g = grad_out;
+  for (size_t i = 0; i < b->pn_cnt.size(); i++) {
+    HIP_TRY(hipMemcpyAsync(g, (const float*)b->dq_grad.p + b->pn_off[i], (size_t)b->pn_cnt[i] * 4,
+                           hipMemcpyDeviceToHost, st));
+    g += b->pn_cnt[i];
+  }
+  double s[kPpoStats];
+  HIP_TRY(hipMemcpyAsync(s, b->pp_stats.p, sizeof(s), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (stats_out) dqn_stats_out(s, 1.0, 1, stats_out);
+  return CPR_OK;
+}
+
+// the indices of gradient step g of update U (include/cpr_hip.h cpr_dqn_update)
+static void dqn_draw(uint64_t seed, uint64_t sample_seed, uint64_t update, uint32_t g,
+                     int64_t batch, int64_t n, int64_t* out) {
+  const uint64_t key = seed ^ (sample_seed * 0x9E3779B97F4A7C15ull);
+  Words4 w = {};
+  for (int64_t i = 0; i < batch; i++) {
+    if ((i & 1) == 0)
+      w = philox4x32_10((uint32_t)update, g, (uint32_t)(i >> 1), TAG_REPLAY, (uint32_t)key,
+                        (uint32_t)(key >> 32));
+    const double u = (i & 1) ? u53(w.w2, w.w3) : u53(w.w0, w.w1);
+    const int64_t j = (int64_t)(u * (double)n);
+    out[i] = j < n - 1 ? j : n - 1;
+  }
+}
+
+int cpr_dqn_update(cpr_batch* b, int32_t gradient_steps, const cpr_dqn_opts* opts,
+                   const int64_t* idx, cpr_dqn_stats* stats_out) {
+  int rc = dqn_check(b, opts);
+  if (rc) return rc;
+  CPR_ENTER(b->ctx);
+  if (gradient_steps < 0) return fail(CPR_E_INVALID_ARG, "dqn: gradient_steps must be >= 0");
+  if (b->dq_size < 1) return fail(CPR_E_STATE, "dqn: the replay ring is empty (cpr_dqn_collect)");
+  const cpr_dqn_opts& o = *opts;
+  hipStream_t st = b->ctx->stream;
+  const int64_t n = b->dq_size * b->cfg.n_lanes, B = o.batch;
+  const size_t cells = (size_t)gradient_steps * (size_t)B;
+  if (stats_out) *stats_out = cpr_dqn_stats{};
+  if (gradient_steps == 0) return CPR_OK;
+  if (idx) {
+    for (size_t i = 0; i < cells; i++)
+      if (idx[i] < 0 || idx[i] >= n)
+        return fail(CPR_E_INVALID_ARG, "dqn: idx outside the ring's written transitions");
+  } else {
+    // drawn here, uploaded behind the kernels already queued; dq_idx_host stays until the
+    // synchronisation at the end of this call
+    b->dq_idx_host.resize(cells);
+    for (int32_t g = 0; g < gradient_steps; g++)
+      dqn_draw(b->cfg.seed, o.sample_seed, (uint64_t)b->dq_updates, (uint32_t)g, B, n,
+               b->dq_idx_host.data() + (size_t)g * (size_t)B);
+  }
+  HIP_TRY(b->dq_idx.ensure(cells * 8));
+  HIP_TRY(hipMemcpyAsync(b->dq_idx.p, idx ? idx : b->dq_idx_host.data(), cells * 8,
+                         hipMemcpyHostToDevice, st));
+  b->dq_idx_n = (int64_t)cells;
+  rc = ppo_scratch(b, B);
+  if (rc) return rc;
+  const DqnRows R = dqn_slot(b, 0);
+  DqnFwd F = {};
+  F.obs32 = R.obs;
+  F.next32 = R.next_obs;
+  F.alpha = R.alpha;
+  F.alpha_col = b->has_env ? b->env.alpha_column : -1;
+  F.action = R.action;
+  F.reward = R.reward;
+  F.done = R.done;
+  F.N = n;
+  F.gamma = o.gamma;
+  double* acc = (double*)b->pp_stats.p + kPpoStats;
+  HIP_TRY(hipMemsetAsync(acc, 0, kPpoStats * 8, st));
+  for (int32_t g = 0; g < gradient_steps; g++) {
+    rc = dqn_minibatch(b, F, (const int64_t*)b->dq_idx.p + (size_t)g * (size_t)B, B, acc);
+    if (rc) return rc;
+    const double t = (double)++b->ppo_t;
+    PpoAdam A = {};
+    A.p = (float*)b->pn_w.p;
+    A.g = (const float*)b->dq_grad.p;
+    A.m = (float*)b->pp_m.p;
+    A.v = (float*)b->pp_v.p;
+    A.n = b->pn_total;
+    A.stats = (const double*)b->pp_stats.p;
+    A.max_norm = (float)o.max_grad_norm;
+    A.b1 = (float)o.beta1;
+    A.omb1 = (float)(1.0 - o.beta1);
+    A.b2 = (float)o.beta2;
+    A.omb2 = (float)(1.0 - o.beta2);
+    A.step = (float)(o.lr / (1.0 - std::pow(o.beta1, t)));
+    A.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(o.beta2, t));
+    A.eps = (float)o.adam_eps;
+    HIP_TRY(launch_adam(A, st));
+  }
+  double s[kPpoStats];
+  HIP_TRY(hipMemcpyAsync(s, acc, sizeof(s), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  ++b->dq_updates;
+  if (stats_out) dqn_stats_out(s, (double)gradient_steps, gradient_steps, stats_out);
+  return CPR_OK;
+}
+
+int cpr_dqn_last_indices(cpr_batch* b, int64_t* out, int64_t n) {
+  int rc = dqn_state(b, true);
+  if (rc) return rc;
+  CPR_ENTER(b->ctx);
+  if (!out) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (n < 1 || n > b->dq_idx_n)
+    return fail(CPR_E_INVALID_ARG, "dqn: more indices than the last update read");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  hipStream_t st = b->ctx->stream;
+  HIP_TRY(hipMemcpyAsync(out, b->dq_idx.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CPR_OK;
+}
+
+int cpr_dqn_target_sync(cpr_batch* b, double tau) {
+  int rc = dqn_state(b, true);
+  if (rc) return rc;
+  CPR_ENTER(b->ctx);
+  if (!(tau >= 0.0 && tau <= 1.0)) return fail(CPR_E_INVALID_ARG, "dqn: tau must be in [0, 1]");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  hipStream_t st = b->ctx->stream;
+  HIP_TRY(launch_polyak((float*)b->dq_tw.p, (const float*)b->pn_w.p, b->pn_total,
+                        (float)(1.0 - tau), (float)tau, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CPR_OK;
+}
+
+int cpr_dqn_iterate(cpr_batch* b, int64_t n_steps, double epsilon, const cpr_dqn_opts* opts,
+                    cpr_summary* summary, cpr_dqn_stats* stats_out) {
+  int rc = dqn_check(b, opts);
+  if (rc) return rc;
+  if (!summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (n_steps < 1) return fail(CPR_E_INVALID_ARG, "dqn: n_steps must be >= 1");
+  const int64_t n = b->cfg.n_lanes;
+  const int64_t every = std::max<int64_t>(opts->target_update_interval / n, 1);
+  const int64_t before = b->dq_steps;
+  rc = cpr_dqn_collect(b, n_steps, epsilon, summary);
+  if (rc) return rc;
+  if (b->dq_steps / every != before / every) {
+    rc = cpr_dqn_target_sync(b, opts->tau);
+    if (rc) return rc;
+  }
+  if (stats_out) *stats_out = cpr_dqn_stats{};
+  if (b->dq_steps * n < opts->learning_starts) return CPR_OK;
+  return cpr_dqn_update(b, opts->gradient_steps, opts, nullptr, stats_out);
+}
+
 int cpr_policy_net_get(cpr_batch* b, cpr_policy_net* net) {
   if (!b || !net) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
   if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
+  return policy_net_read(b, b->pn_w.p, net);
+}
+
+// a parameter buffer in the network's padded layout (the weights, or Q-learning's target) into
+// the caller's arrays
+static int policy_net_read(cpr_batch* b, const void* weights, cpr_policy_net* net) {
   const PolNet& N = b->pn;
   std::vector<float*> dst;
   for (int trunk = 0; trunk < 2; trunk++) {
@@ -3925,7 +4470,7 @@ int cpr_policy_net_get(cpr_batch* b, cpr_policy_net* net) {
   HIP_TRY(hipSetDevice(b->ctx->device));
   hipStream_t st = b->ctx->stream;
   for (size_t i = 0; i < dst.size(); i++)
-    HIP_TRY(hipMemcpyAsync(dst[i], (const float*)b->pn_w.p + b->pn_off[i], (size_t)b->pn_cnt[i] * 4,
+    HIP_TRY(hipMemcpyAsync(dst[i], (const float*)weights + b->pn_off[i], (size_t)b->pn_cnt[i] * 4,
                            hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return CPR_OK;

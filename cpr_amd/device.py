@@ -858,6 +858,139 @@ class Batch:
                                         ctypes.byref(st)))
         return s, st.as_dict()
 
+    # ---- Q-learning (cpr_dqn_*; DESIGN.md §4.14 "Q-learning")
+    DQN_DATA = ("obs", "alpha", "action", "reward", "done", "next_obs")
+
+    @staticmethod
+    def _dqn_opts(options):
+        from .dqn import DQNOptions
+
+        o = options if options is not None else DQNOptions()
+        return o.cstruct()
+
+    def dqn_init(self, capacity_steps):
+        """The replay ring of ``capacity_steps`` slots of ``n_lanes`` transitions and the target
+        network, a copy of the current weights (cpr_dqn_init)."""
+        L.check(L.lib().cpr_dqn_init(self.handle, int(capacity_steps)))
+
+    def dqn_collect(self, n_steps, epsilon, summary=None):
+        """``n_steps`` epsilon-greedy steps of every lane into the ring (cpr_dqn_collect).
+        Returns the rollout's summary."""
+        s = summary if summary is not None else L.Summary()
+        L.check(L.lib().cpr_dqn_collect(self.handle, int(n_steps), float(epsilon), ctypes.byref(s)))
+        return s
+
+    def dqn_replay_state(self):
+        """(size, cursor, capacity) of the ring, in slots."""
+        v = [ctypes.c_int64() for _ in range(3)]
+        L.check(L.lib().cpr_dqn_replay_state(self.handle, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def dqn_replay(self, first_slot=0, n_slots=None):
+        """Slots [first_slot, first_slot + n_slots) of the ring (cpr_dqn_replay_get; default:
+        the written ones) as a dict of arrays shaped [n_slots, n_lanes, ...] with the keys of
+        ``DQN_DATA``. Slot ``capacity`` is the guard slot behind the ring."""
+        if n_slots is None:
+            n_slots = self.dqn_replay_state()[0] - first_slot
+        n_slots, n = int(n_slots), self.n_lanes
+        out = {"obs": np.zeros((n_slots, n, self.obs_len)), "alpha": np.zeros((n_slots, n)),
+               "action": np.zeros((n_slots, n), dtype=np.int32), "reward": np.zeros((n_slots, n)),
+               "done": np.zeros((n_slots, n), dtype=np.uint8),
+               "next_obs": np.zeros((n_slots, n, self.obs_len))}
+        c = L.DqnDataC()
+        for k, v in out.items():
+            setattr(c, k, v.ctypes.data)
+        L.check(L.lib().cpr_dqn_replay_get(self.handle, int(first_slot), n_slots, ctypes.byref(c)))
+        return out
+
+    def _dqn_data(self, data):
+        c = L.DqnDataC()
+        dt = {"obs": np.float64, "alpha": np.float64, "action": np.int32, "reward": np.float64,
+              "done": np.uint8, "next_obs": np.float64}
+        keep = {}
+        for k in self.DQN_DATA:
+            v = data.get(k)
+            if v is None:
+                if k != "alpha":
+                    raise ValueError(f"data: {k!r} is missing")
+                continue
+            keep[k] = np.ascontiguousarray(v, dtype=dt[k])
+        n = keep["action"].size
+        for k in ("obs", "next_obs"):
+            keep[k] = keep[k].reshape(-1, self.obs_len)
+        for k in ("alpha", "action", "reward", "done"):
+            if k in keep:
+                keep[k] = keep[k].reshape(-1)
+        for k, v in keep.items():
+            if v.shape[0] != n:
+                raise ValueError(f"data: {k!r} has shape {list(v.shape)}, expected {n} rows")
+            setattr(c, k, v.ctypes.data)
+        c.n = n
+        c.on_device = 0
+        return c, keep
+
+    def dqn_gradients(self, data, rows, options=None):
+        """The Q-learning gradient of the transitions ``rows`` (indices into ``data``, a dict of
+        host arrays with the keys of ``DQN_DATA``, ``alpha`` optional) without touching the
+        weights: (flat f32 gradient in ``cpr_amd.ppo.param_arrays`` order, statistics dict)."""
+        o = self._dqn_opts(options)
+        c, keep = self._dqn_data(data)
+        ia = np.ascontiguousarray(rows, dtype=np.int64).ravel()
+        grad = np.zeros(self.ppo_param_count(), dtype=np.float32)
+        st = L.DqnStats()
+        L.check(L.lib().cpr_dqn_gradients(self.handle, ctypes.byref(c), L.ptr(ia), ia.size,
+                                          ctypes.byref(o), L.ptr(grad), ctypes.byref(st)))
+        del keep
+        return grad, st.as_dict()
+
+    def dqn_update(self, gradient_steps=None, options=None, idx=None):
+        """``gradient_steps`` (default: the options') steps of gradient, clip and Adam on the
+        ring (cpr_dqn_update). ``idx``: integers [gradient_steps, batch] of flat transition
+        indices slot * n_lanes + lane, or None for the library's keyed draws. Returns the
+        update's statistics dict."""
+        o = self._dqn_opts(options)
+        g = int(o.gradient_steps if gradient_steps is None else gradient_steps)
+        ia = None
+        if idx is not None:
+            ia = np.ascontiguousarray(idx, dtype=np.int64)
+            if ia.shape != (g, o.batch):
+                raise ValueError(f"idx: expected [{g}, {o.batch}], got {list(ia.shape)}")
+        st = L.DqnStats()
+        L.check(L.lib().cpr_dqn_update(self.handle, g, ctypes.byref(o), L.ptr(ia),
+                                       ctypes.byref(st)))
+        return st.as_dict()
+
+    def dqn_last_indices(self, gradient_steps, batch):
+        """The indices the last ``dqn_update`` read, [gradient_steps, batch], from the device."""
+        out = np.zeros((int(gradient_steps), int(batch)), dtype=np.int64)
+        L.check(L.lib().cpr_dqn_last_indices(self.handle, L.ptr(out), out.size))
+        return out
+
+    def dqn_target_sync(self, tau=1.0):
+        """target = (1 - tau) target + tau weights, SB3's polyak_update (cpr_dqn_target_sync)."""
+        L.check(L.lib().cpr_dqn_target_sync(self.handle, float(tau)))
+
+    def dqn_iterate(self, n_steps, epsilon, options=None, summary=None):
+        """One DQN iteration on the device (cpr_dqn_iterate): collect, the target update when
+        its interval was crossed, the gradient steps once learning has started. Returns
+        (summary of the rollout, statistics dict; ``n_steps`` 0 if no update ran)."""
+        o = self._dqn_opts(options)
+        s = summary if summary is not None else L.Summary()
+        st = L.DqnStats()
+        L.check(L.lib().cpr_dqn_iterate(self.handle, int(n_steps), float(epsilon), ctypes.byref(o),
+                                        ctypes.byref(s), ctypes.byref(st)))
+        return s, st.as_dict()
+
+    def get_target_net(self):
+        """The target network as a ``PolicyNet`` (cpr_dqn_target_get)."""
+        net = getattr(self, "_net", None)
+        if net is None:
+            raise L.CprError(L.CPR_E_STATE, "no policy network set (set_policy_net)")
+        out = net.zeros_like()
+        c = out.cstruct()
+        L.check(L.lib().cpr_dqn_target_get(self.handle, ctypes.byref(c)))
+        return out
+
     def get_policy_net(self):
         """The batch's current weights as a ``PolicyNet`` (cpr_policy_net_get)."""
         net = getattr(self, "_net", None)

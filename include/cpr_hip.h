@@ -73,7 +73,8 @@ enum cpr_protocol {
                              of (a, h, fork), unit_observation ignored; done = terminated, or
                              max_steps steps: CPR_ST_CAPACITY), cpr_observe_fields (a, h, fork),
                              the policy network, cpr_rollout_net(_env), the lane env, the
-                             learner and cpr_eval_net. CPR_E_UNSUPPORTED: cpr_rollout,
+                             learner, Q-learning (cpr_dqn_*) and cpr_eval_net.
+                             CPR_E_UNSUPPORTED: cpr_rollout,
                              cpr_policy_actions, cpr_replay, cpr_node_outputs and
                              CPR_GYM_REWARD_DENSE_PER_PROGRESS (no progress target) */
 };
@@ -849,6 +850,115 @@ int cpr_ppo_update(cpr_batch* b, const cpr_ppo_data* data, const cpr_ppo_opts* o
  * n_steps * n_lanes rows. Bit for bit what the three calls give when composed by hand. */
 int cpr_ppo_iterate(cpr_batch* b, int64_t n_steps, const cpr_ppo_opts* opts,
                     cpr_summary* summary, cpr_ppo_stats* stats_out);
+
+/* Q-learning (added within v11; a batch that never calls these launches what it did before):
+ * SB3's DQN as gym/rust/hyperparams/dqn.yml configures it, on the batch's device weights.
+ * DESIGN.md §4.14 "Q-learning" has the loss, every order and the deviations from SB3.
+ *
+ * The Q-network is the batch's policy network: Q(s, a) = logit a of the pi trunk and its head.
+ * The vf trunk takes no part: the DQN kernels skip it, its gradient is exactly zero and its
+ * weights keep their bytes. The greedy policy is deterministic = 1 of the existing forward.
+ * Adam's moments and step count are the learner's (shared with cpr_ppo_update). */
+typedef struct cpr_dqn_opts {
+  int64_t batch;                  /* >= 1 rows per gradient step */
+  int32_t gradient_steps;         /* >= 0 per cpr_dqn_iterate */
+  double gamma;
+  double lr;
+  double beta1, beta2, adam_eps;
+  double max_grad_norm;
+  double tau;                     /* cpr_dqn_iterate's Polyak weight, in [0, 1] */
+  int64_t target_update_interval; /* in transitions; / n_lanes in vector steps */
+  int64_t learning_starts;        /* in transitions */
+  uint64_t sample_seed;
+} cpr_dqn_opts;
+/* dqn.yml's default block over SB3's: batch 32, 1 gradient step, gamma 0.99, lr 1e-4, betas
+ * (0.9, 0.999), eps 1e-8, max-norm 10, tau 1, interval 10,000, learning_starts 50,000, seed 0 */
+int cpr_dqn_opts_default(cpr_dqn_opts* opts);
+
+/* n transitions: the policy input, the lane alpha of the row (read only when the batch's lane
+ * env names an alpha column; it is next_obs' alpha too), the action, the reward, done and the
+ * next policy input. Host pointers, or device pointers if on_device != 0. */
+typedef struct cpr_dqn_data {
+  int64_t n;
+  const double* obs;      /* [n][obs_len] */
+  const double* alpha;    /* [n] or NULL */
+  const int32_t* action;  /* [n] */
+  const double* reward;   /* [n] */
+  const uint8_t* done;    /* [n] */
+  const double* next_obs; /* [n][obs_len] */
+  int32_t on_device;
+} cpr_dqn_data;
+
+/* row means of a gradient step, or their mean over an update's steps (stream order) */
+typedef struct cpr_dqn_stats {
+  double loss;      /* mean smooth_l1(q_a - y), beta = 1 */
+  double abs_td;    /* mean |q_a - y| */
+  double q;         /* mean q_a */
+  double target;    /* mean y */
+  double grad_norm; /* global L2 norm before the clip */
+  int64_t n_steps;  /* gradient steps behind the means; 0: no update ran */
+} cpr_dqn_stats;
+
+/* The replay ring: capacity_steps slots of n_lanes transitions (SB3's buffer_size // n_envs),
+ * the inputs stored in f32 (the forward rounds to f32 first, so a stored row gives the Q-values
+ * of the original f64 row bit for bit). The target network becomes a copy of the weights; the
+ * slot cursor, the size, the counts of collected steps and of updates, and Adam's state are
+ * zeroed. CPR_E_STATE without a network; CPR_E_UNSUPPORTED where cpr_policy_net_set is;
+ * capacity_steps < 1 is CPR_E_INVALID_ARG. A later cpr_policy_net_set / _copy keeps the ring and
+ * makes the target a copy of the new weights. */
+int cpr_dqn_init(cpr_batch* b, int64_t capacity_steps);
+
+/* cpr_rollout_net_env's per-step launch sequence (forward, step kernels, collect, masked reset;
+ * never the one-kernel FC16 rollout) with an epsilon-greedy action: of the keyed block
+ * ctr = (episode, episode step index before the step, 0x90000000), key = seed,
+ * u1 = u53(w0, w1), u2 = u53(w2, w3); u1 < epsilon: min(n_actions - 1, (int)(u2 n_actions)),
+ * else the lowest index of the maximum. Step t of the call goes to slot (cursor + t) mod
+ * capacity; size = min(capacity, size + n_steps). The reward is the lane env's if one is set;
+ * next_obs is the observation after the step's auto-reset. epsilon = 0 is
+ * cpr_rollout_net_env(deterministic = 1) bit for bit. One synchronisation, at the end. */
+int cpr_dqn_collect(cpr_batch* b, int64_t n_steps, double epsilon, cpr_summary* summary);
+
+/* The gradient of one minibatch (rows rows_idx[0 .. n_rows) of data, int64; a device pointer if
+ * data->on_device) and its statistics; the weights stay. Needs cpr_dqn_init (the target). grad_out: cpr_ppo_gradients' flat order, cpr_ppo_param_count floats (the vf
+ * trunk's are zero). Only opts->gamma is read. Per row, f64, one rounding per operation:
+ *   q' = max_i target(next_obs)_i;  y = reward + (gamma q') (1 - done);  d = q_a - y
+ *   l = 0.5 d^2 if |d| < 1 else |d| - 0.5;  dL/dq_a = clamp(d, -1, 1) / n_rows */
+int cpr_dqn_gradients(cpr_batch* b, const cpr_dqn_data* data, const int64_t* rows_idx,
+                      int64_t n_rows, const cpr_dqn_opts* opts, float* grad_out,
+                      cpr_dqn_stats* stats_out);
+
+/* gradient_steps steps of gradient (opts->batch rows of the ring), global-norm clip and Adam, no
+ * host synchronisation between them. idx: int64 [gradient_steps][batch] flat transition
+ * indices slot * n_lanes + lane (host), each < size * n_lanes. idx == NULL: row i of step g of
+ * update U (the count of cpr_dqn_update calls since cpr_dqn_init / cpr_policy_net_set) is
+ *   min(n - 1, (int64)(u n)), n = size * n_lanes, u = u53 of words 2 (i & 1), + 1 of block
+ *   ctr = (U, g, i >> 1, 0xA0000000), key = seed ^ sample_seed * 0x9E3779B97F4A7C15
+ * CPR_E_STATE: no cpr_dqn_init, or an empty ring. gradient_steps = 0 does nothing. */
+int cpr_dqn_update(cpr_batch* b, int32_t gradient_steps, const cpr_dqn_opts* opts,
+                   const int64_t* idx, cpr_dqn_stats* stats_out);
+/* the indices the last cpr_dqn_update read, copied back from the device: the first n of
+ * [gradient_steps][batch] */
+int cpr_dqn_last_indices(cpr_batch* b, int64_t* out, int64_t n);
+
+/* SB3's polyak_update, elementwise in f32: t = (t omt) + (p tf), omt = (float)(1 - tau),
+ * tf = (float)tau, one rounding per product and one for the sum; tau = 1 copies the bytes. */
+int cpr_dqn_target_sync(cpr_batch* b, double tau);
+
+/* cpr_dqn_collect; then cpr_dqn_target_sync(opts->tau) once if the batch's collected vector
+ * steps crossed a multiple of max(target_update_interval / n_lanes, 1) during it; then
+ * cpr_dqn_update(opts->gradient_steps, idx NULL) if the collected transitions have reached
+ * learning_starts (else stats_out->n_steps = 0). Bit for bit the three calls by hand. */
+int cpr_dqn_iterate(cpr_batch* b, int64_t n_steps, double epsilon, const cpr_dqn_opts* opts,
+                    cpr_summary* summary, cpr_dqn_stats* stats_out);
+
+/* Slots [first_slot, first_slot + n_slots) of the ring into out's arrays (host, writable
+ * despite the const; alpha may be NULL), n_slots * n_lanes rows. Slot `capacity_steps` is a
+ * guard slot behind the ring that no collect writes (cpr_dqn_init fills it with 0xA5 bytes).
+ * size / cursor / capacity (optional): the ring's state in slots. */
+int cpr_dqn_replay_get(cpr_batch* b, int64_t first_slot, int64_t n_slots, cpr_dqn_data* out);
+int cpr_dqn_replay_state(cpr_batch* b, int64_t* size, int64_t* cursor, int64_t* capacity);
+/* the target network, as cpr_policy_net_get */
+int cpr_dqn_target_get(cpr_batch* b, cpr_policy_net* net);
 
 /* The batch's current weights into the caller's arrays, laid out as for cpr_policy_net_set
  * (every array pointer of `net` must be writable despite the const; n_extra, extra, depth

@@ -314,6 +314,55 @@ let ppo_iterate =
 
 let policy_net_get = foreign "cpr_policy_net_get" (ptr batch @-> ptr void @-> returning int)
 
+(* Q-learning (added within ABI v11): cpr_dqn_opts, cpr_dqn_data and cpr_dqn_stats are untyped
+   pointers to caller-built C structs (include/cpr_hip.h) *)
+let dqn_opts_default = foreign "cpr_dqn_opts_default" (ptr void @-> returning int)
+let dqn_init = foreign "cpr_dqn_init" (ptr batch @-> int64_t @-> returning int)
+
+let dqn_collect =
+  foreign "cpr_dqn_collect" (ptr batch @-> int64_t @-> double @-> ptr summary @-> returning int)
+;;
+
+let dqn_gradients =
+  foreign
+    "cpr_dqn_gradients"
+    (ptr batch @-> ptr void @-> ptr int64_t @-> int64_t @-> ptr void @-> ptr float @-> ptr void
+    @-> returning int)
+;;
+
+let dqn_update =
+  foreign
+    "cpr_dqn_update"
+    (ptr batch @-> int32_t @-> ptr void @-> ptr int64_t @-> ptr void @-> returning int)
+;;
+
+let dqn_last_indices =
+  foreign "cpr_dqn_last_indices" (ptr batch @-> ptr int64_t @-> int64_t @-> returning int)
+;;
+
+let dqn_target_sync = foreign "cpr_dqn_target_sync" (ptr batch @-> double @-> returning int)
+
+let dqn_iterate =
+  foreign
+    "cpr_dqn_iterate"
+    (ptr batch @-> int64_t @-> double @-> ptr void @-> ptr summary @-> ptr void
+    @-> returning int)
+;;
+
+let dqn_replay_get =
+  foreign
+    "cpr_dqn_replay_get"
+    (ptr batch @-> int64_t @-> int64_t @-> ptr void @-> returning int)
+;;
+
+let dqn_replay_state =
+  foreign
+    "cpr_dqn_replay_state"
+    (ptr batch @-> ptr int64_t @-> ptr int64_t @-> ptr int64_t @-> returning int)
+;;
+
+let dqn_target_get = foreign "cpr_dqn_target_get" (ptr batch @-> ptr void @-> returning int)
+
 (* evaluation (added within ABI v11): the cyclic assumption schedule (0 = choice, 1 = cycle),
    whole episodes with per-alpha results (cpr_eval_opts, cpr_eval_record and cpr_eval_alpha
    are untyped pointers to caller-built C structs) and the device-to-device weight copy *)

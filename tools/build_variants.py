@@ -57,7 +57,7 @@ def main():
 
 
 ALL = ["kernels.hip", "kernels_nak_fused.hip", "kernels_nak_rollout.hip", *EV, "kernels_fc16.hip",
-       "kernels_policy.hip", "kernels_ppo.hip"]
+       "kernels_policy.hip", "kernels_ppo.hip", "kernels_dqn.hip"]
 
 
 def build_def(objdir, out, flags, tag, tus, defs):

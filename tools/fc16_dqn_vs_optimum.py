@@ -1,0 +1,134 @@
+"""Device Q-learning against ground truth: DQN on the FC16 env (CPR_PROTO_FC16_ENV), the
+greedy policy of the Q-network tabulated after every iteration (mdp.fc16_table_from_net) and
+the table's exact expected episode reward (mdp.fc16_policy_value: no Monte Carlo noise)
+recorded beside the exact values of honest play, SM1 and the value-iteration table. The DQN
+twin of tools/fc16_ppo_vs_optimum.py, with the same env, table and border.
+
+alpha .4, gamma .5, horizon 25. dqn.yml's FC16SSZwPT-v0 hyperparameters (cpr_amd.dqn.FC16_PRESET:
+batch 500, 100 gradient steps per iteration, lr 1e-3, discount 1, tau 0.01, epsilon 1 -> 0.1
+over the first tenth) on --lanes lanes: --steps vector steps per iteration (the preset's
+train_freq is 10,000 transitions), a ring of --capacity slots, learning from --learning-starts
+transitions on. Reports the curve; gates on nothing. Prints one JSON line and writes it to --out
+(default profiles/fc16_dqn_vs_optimum.json)."""
+import argparse
+import dataclasses
+import json
+import pathlib
+import sys
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+import numpy as np  # noqa: E402
+
+from cpr_amd import _lib as L, device, dqn, mdp  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--lanes", type=int, default=1024)
+ap.add_argument("--steps", type=int, default=10)
+ap.add_argument("--iterations", type=int, default=60)
+ap.add_argument("--capacity", type=int, default=512)
+ap.add_argument("--learning-starts", type=int, default=20_480)
+ap.add_argument("--width", type=int, default=64)
+ap.add_argument("--depth", type=int, default=2)
+ap.add_argument("--dim", type=int, default=24)
+ap.add_argument("--seed", type=int, default=1)
+ap.add_argument("--out", default=str(ROOT / "profiles" / "fc16_dqn_vs_optimum.json"))
+args = ap.parse_args()
+ALPHA, GAMMA, HORIZON, DIM = 0.4, 0.5, 25, args.dim
+
+
+def honest(a, h):
+    return mdp.FC16_OVERRIDE if a > h else (mdp.FC16_ADOPT if h > a else mdp.FC16_WAIT)
+
+
+def sm1(a, h):
+    if h > a:
+        return mdp.FC16_ADOPT
+    if h == 1 and a == 1:
+        return mdp.FC16_MATCH
+    if h == a - 1 and h >= 1:
+        return mdp.FC16_OVERRIDE
+    return mdp.FC16_WAIT
+
+
+def table_of(fn):
+    t = np.zeros((DIM, DIM, 3), np.uint8)
+    for a in range(DIM):
+        for h in range(DIM):
+            t[a, h, :] = fn(a, h)
+    return t.ravel()
+
+
+def with_honest_border(table):
+    t = np.array(table, np.uint8).reshape(DIM, DIM, 3)
+    for x in range(DIM):
+        t[DIM - 1, x, :] = honest(DIM - 1, x)
+        t[x, DIM - 1, :] = honest(x, DIM - 1)
+    return t.ravel()
+
+
+def value(table):
+    v, g = mdp.fc16_policy_value(ALPHA, GAMMA, HORIZON, table)
+    return dict(reward=float(v), progress=float(g), reward_per_progress=float(v / g))
+
+
+preset = dqn.FC16_PRESET
+opts = dataclasses.replace(preset["options"], learning_starts=args.learning_starts,
+                           target_update_interval=args.lanes * args.steps)
+res = dict(setup=dict(alpha=ALPHA, gamma=GAMMA, horizon=HORIZON, lanes=args.lanes,
+                      steps_per_iteration=args.steps, iterations=args.iterations,
+                      capacity_steps=args.capacity, network=f"{args.depth}x{args.width}",
+                      options=dataclasses.asdict(opts),
+                      epsilon=[preset["exploration_initial_eps"], preset["exploration_final_eps"],
+                               preset["exploration_fraction"]],
+                      table_dim=DIM, border="honest play where a or h = dim - 1"))
+res["honest"] = value(table_of(honest))
+res["sm1"] = value(with_honest_border(table_of(sm1)))
+vi = mdp.fc16_table(ALPHA, GAMMA, dim=DIM, maximum_fork_length=DIM - 1, horizon=HORIZON)
+res["value_iteration"] = value(with_honest_border(vi))
+
+
+def main():
+    """The GPU part. The batch and the context are closed before the interpreter exits."""
+    ctx = device.Context(0)
+    cfg, keep = device.make_config(protocol=L.PROTO_FC16_ENV, alpha=ALPHA, gamma=GAMMA,
+                                   horizon=HORIZON, max_steps=254, seed=args.seed,
+                                   n_lanes=args.lanes, policy=L.FC16_POLICY_HONEST)
+    b = device.Batch(cfg, ctx=ctx, keep=keep)
+    rng = np.random.default_rng(args.seed)
+
+    def lin(n_out, fan_in, scale=1.0):
+        return ((scale * rng.standard_normal((n_out, fan_in)) / np.sqrt(fan_in)).astype(np.float32),
+                np.zeros(n_out, np.float32))
+
+    def trunk():
+        return [lin(args.width, 3 if i == 0 else args.width) for i in range(args.depth)]
+
+    b.set_policy_net(device.PolicyNet(pi=trunk(), pi_head=lin(4, args.width, 0.01), vf=trunk(),
+                                      vf_head=lin(1, args.width)))
+    b.dqn_init(args.capacity)
+    eps = dqn.epsilon_schedule(preset["exploration_initial_eps"], preset["exploration_final_eps"],
+                               preset["exploration_fraction"])
+    curve = [dict(iteration=0, **value(with_honest_border(
+        mdp.fc16_table_from_net(b.get_policy_net(), DIM, ctx=ctx))))]
+    run = dqn.train(b, args.iterations, args.steps, opts, epsilon=eps)
+    for it, (summary, stats) in enumerate(run, 1):
+        row = value(with_honest_border(mdp.fc16_table_from_net(b.get_policy_net(), DIM, ctx=ctx)))
+        row.update(iteration=it, episodes=int(summary.episodes), epsilon=stats["epsilon"],
+                   gradient_steps=stats["n_steps"], loss=stats["loss"], q=stats["q"])
+        curve.append(row)
+        print(f"# {it}: E[reward] {row['reward']:.4f}  (honest {res['honest']['reward']:.4f}, sm1 "
+              f"{res['sm1']['reward']:.4f}, vi {res['value_iteration']['reward']:.4f})",
+              file=sys.stderr, flush=True)
+    res["curve"] = curve
+    line = json.dumps(res)
+    print(line, flush=True)
+    out = pathlib.Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(line + "\n")
+    b.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -96,6 +96,10 @@ HIST_BINS = 64
 # tests/test_gpu_fused_points.py test_group_sizes* fail if the library groups otherwise)
 NAK_FUSE_MAX = 5
 NAK_FUSE_MAX_ARR = 2
+# lanes per episode of a full lane-group launch (csrc/nak_fused.h CPR_NAK_FUSE_LANES,
+# CPR_NAK_FUSE_LANES_ARR; tests/test_gpu_lane_groups.py fails if the library cuts otherwise)
+NAK_FUSE_LANES = 2
+NAK_FUSE_LANES_ARR = 4
 
 
 class Config(ctypes.Structure):

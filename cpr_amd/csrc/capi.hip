@@ -1534,6 +1534,18 @@ static int fuse_cap(int kind) {
   return std::max(0, std::min(cap, kind == 2 ? kFuseMaxArr : kFuseMax));
 }
 
+// the lanes of a lane group (nak_fused.h): the largest built power of two that
+// CPR_NAK_FUSE_LANES (read at every call) allows; 1: none, every lane its own episode. Lane
+// groups are built with full lanes only, so a smaller CPR_NAK_FUSE leaves none
+static int fuse_lanes(int kind, int cap) {
+  if (cap < 1 || cap != (kind == 2 ? kFuseMaxArr : kFuseMax)) return 1;
+  int g = kind == 2 ? kFuseLanesArr : kFuseLanes;
+  if (const char* v = getenv("CPR_NAK_FUSE_LANES")) g = std::min(g, atoi(v));
+  int p = 1;
+  while (2 * p <= g) p *= 2;
+  return p;
+}
+
 // which of the instantiations the fused kernel stands for a call would run (0: neither)
 static int fuse_kind(const cpr_batch* b, const cpr_episode_record* rec_dev) {
   if (b->cfg.protocol != CPR_PROTO_NAKAMOTO || b->nak_ev || b->is_ev || b->is_eth) return 0;
@@ -1558,33 +1570,24 @@ static bool fuse_same_launch(const cpr_batch* a, const cpr_batch* b) {
          a->NEP.cap_b == b->NEP.cap_b && a->NEP.cap_e == b->NEP.cap_e && a->NEP.n == b->NEP.n;
 }
 
-static int fuse_launch_pending(cpr_ctx* c) {
-  if (c->fuse.empty()) return CPR_OK;
-  // emptied first: whatever fails below, the group is not launched twice
-  std::vector<cpr_ctx::FuseMember> g;
-  g.swap(c->fuse);
-  const int64_t n = c->fuse_n;
-  const uint64_t first = c->fuse_first;
-  HIP_TRY(hipSetDevice(c->device));
-  const int na = (int)g.size();
-  if (na == 1) {
-    g[0].b->async_launch = true;
-    return run_async(g[0].b, n, first, nullptr, g[0].sum, nullptr);
-  }
+// one k_run_episodes_fused launch: na points per lane, gl lanes per episode, np = na * gl
+// members (np >= 2)
+static int fuse_launch_group(cpr_ctx* c, const cpr_ctx::FuseMember* g, int na, int gl, int kind,
+                             int64_t n, uint64_t first) {
+  const int np = na * gl;
   cpr_batch* b0 = g[0].b;
   // every member's re-run registration before the kernel. A flush in the middle would drop
   // the registrations made so far, so where the launch table or the overflow-flag chunks
   // may not hold the whole group, the flush comes first, before the group's kernel on the
   // stream, and the group registers into the emptied table
-  const int kind = c->fuse_kind;
-  FusePoint pts[kFuseMax > kFuseMaxArr ? kFuseMax : kFuseMaxArr];
+  FusePoint pts[kFusePoints];
   int64_t* redo = nullptr;
   uint32_t* redo_n = nullptr;
   if (b0->has_rerun) {
-    if (!rerun_room(c, n, na)) {
+    if (!rerun_room(c, n, np)) {
       if (const int rc = flush_reruns(c)) return rc;
     }
-    for (int i = 0; i < na; ++i) {
+    for (int i = 0; i < np; ++i) {
       cpr_batch* b = g[i].b;
       NakParams NP;
       const bool hyb = rerun_hybrid(b, false, &NP);
@@ -1593,7 +1596,7 @@ static int fuse_launch_pending(cpr_ctx* c) {
                                         &pts[i].ovf, hyb ? &NP : nullptr))
         return rc;
     }
-    if (pts[na - 1].launch_id != pts[0].launch_id + (uint32_t)(na - 1))
+    if (pts[np - 1].launch_id != pts[0].launch_id + (uint32_t)(np - 1))
       return fail(CPR_E_HIP, "re-run table flushed while a group registered");
   }
   // deferred races: one list region per member in one of the context's two list buffers
@@ -1603,13 +1606,13 @@ static int fuse_launch_pending(cpr_ctx* c) {
   const int li = c->list_i;
   if (kind == 2) {
     if (c->list_pending[li]) {
-      if (c->lists[li].bytes < list_bytes * na) HIP_TRY(hipEventSynchronize(c->list_ev[li]));
+      if (c->lists[li].bytes < list_bytes * np) HIP_TRY(hipEventSynchronize(c->list_ev[li]));
       HIP_TRY(hipStreamWaitEvent(c->stream, c->list_ev[li], 0));
       c->list_pending[li] = false;
     }
-    HIP_TRY(c->lists[li].ensure(list_bytes * na));
+    HIP_TRY(c->lists[li].ensure(list_bytes * np));
   }
-  for (int i = 0; i < na; ++i) {
+  for (int i = 0; i < np; ++i) {
     pts[i].t_att = g[i].b->P.t_att;
     pts[i].sum = g[i].sum;
     pts[i].list = kind == 2 ? (int64_t*)((uint8_t*)c->lists[li].p + list_bytes * i) : nullptr;
@@ -1618,17 +1621,18 @@ static int fuse_launch_pending(cpr_ctx* c) {
       pts[i].launch_id = 0;
     }
   }
-  const int bpc = run_episodes_fused_blocks_per_cu(b0->P, na);
-  const int64_t lanes = episode_lanes(b0, n, bpc);
+  const int bpc = run_episodes_fused_blocks_per_cu(b0->P, na, gl);
+  // gl lanes per episode
+  const int64_t lanes = episode_lanes(b0, n * gl, bpc);
   auto ft = std::make_shared<FuseTime>();
-  ft->size = na;
+  ft->size = np;
   HIP_TRY(hipEventCreate(&ft->ev0));
   HIP_TRY(hipEventCreate(&ft->ev1));
   NakParams P = b0->P;
   const char* wq = getenv("CPR_NAK_WQ");
   if (!(wq && wq[0] == '0')) HIP_TRY(ctx_next(c, &P.next));
   HIP_TRY(hipEventRecord(ft->ev0, c->stream));
-  HIP_TRY(launch_run_episodes_fused(P, b0->cfg.seed, first, n, pts, na, lanes, redo, redo_n,
+  HIP_TRY(launch_run_episodes_fused(P, b0->cfg.seed, first, n, pts, na, gl, lanes, redo, redo_n,
                                     c->rq_cap, c->stream));
   // the group's time is its kernel's, on the stream. The second passes below are not in it:
   // on the side stream they share the device with the next launch and mostly wait for its
@@ -1641,7 +1645,7 @@ static int fuse_launch_pending(cpr_ctx* c) {
         episode_lanes(b0, n, run_episodes_blocks_per_cu(b0->P, b0->cfg.mode, false));
     HIP_TRY(hipEventRecord(c->main_ev, c->stream));
     HIP_TRY(hipStreamWaitEvent(c->side, c->main_ev, 0));
-    for (int i = 0; i < na; ++i)
+    for (int i = 0; i < np; ++i)
       HIP_TRY(launch_run_episodes_second(g[i].b->P, b0->cfg.seed, first, n, pts[i].list, lanes2,
                                          g[i].sum, redo, redo_n, pts[i].launch_id, c->rq_cap,
                                          pts[i].ovf, c->side));
@@ -1649,12 +1653,44 @@ static int fuse_launch_pending(cpr_ctx* c) {
     c->list_pending[li] = true;
     c->list_i ^= 1;
   }
-  for (int i = 0; i < na; ++i) {
+  for (int i = 0; i < np; ++i) {
     cpr_batch* b = g[i].b;
     b->last_lanes = lanes;
     b->last_resident = (int64_t)c->cus * bpc * 256;
     b->fuse_time = ft;
     b->async_launch = true;
+  }
+  return CPR_OK;
+}
+
+// The pending members, in call order, cut greedily: first into full lane-group launches
+// (every lane full: NAmax points per lane x the largest lane group CPR_NAK_FUSE_LANES
+// allows), the rest into groups of up to NAmax points in one lane each, a single member as
+// the one-point kernel
+static int fuse_launch_pending(cpr_ctx* c) {
+  if (c->fuse.empty()) return CPR_OK;
+  // emptied first: whatever fails below, the group is not launched twice
+  std::vector<cpr_ctx::FuseMember> g;
+  g.swap(c->fuse);
+  const int64_t n = c->fuse_n;
+  const uint64_t first = c->fuse_first;
+  HIP_TRY(hipSetDevice(c->device));
+  const int kind = c->fuse_kind;
+  const int namax = std::max(1, fuse_cap(kind));
+  int gl = fuse_lanes(kind, namax);
+  const int m = (int)g.size();
+  int i = 0;
+  while (i < m) {
+    if (m - i < namax * gl) gl = 1;
+    const int np = gl > 1 ? namax * gl : std::min(namax, m - i);
+    if (np == 1) {
+      g[i].b->async_launch = true;
+      if (const int rc = run_async(g[i].b, n, first, nullptr, g[i].sum, nullptr)) return rc;
+    } else if (const int rc = fuse_launch_group(c, &g[i], gl > 1 ? namax : np, gl, kind, n,
+                                                first)) {
+      return rc;
+    }
+    i += np;
   }
   return CPR_OK;
 }
@@ -1666,7 +1702,8 @@ int cpr_run_episodes_async(cpr_batch* b, int64_t n, uint64_t first, cpr_summary*
   cpr_ctx* c = b->ctx;
   const int kind = fuse_kind(b, rec_dev);
   const int cap = fuse_cap(kind);
-  const bool fusable = kind != 0 && cap >= 2;
+  // (a build with one point per lane groups through its lane groups alone)
+  const bool fusable = kind != 0 && cap >= 1 && cap * fuse_lanes(kind, cap) >= 2;
   // the pending group is launched before any call that does not join it is handled
   if (!c->fuse.empty() && !(fusable && n == c->fuse_n && first == c->fuse_first &&
                             fuse_same_launch(c->fuse[0].b, b)))
@@ -1676,7 +1713,8 @@ int cpr_run_episodes_async(cpr_batch* b, int64_t n, uint64_t first, cpr_summary*
     c->fuse_kind = kind;
     c->fuse_n = n;
     c->fuse_first = first;
-    if ((int)c->fuse.size() >= cap) CPR_ENTER(c);
+    // the pending group grows to one full lane-group launch (points per lane x lanes)
+    if ((int)c->fuse.size() >= cap * fuse_lanes(kind, cap)) CPR_ENTER(c);
     return CPR_OK;
   }
   HIP_TRY(hipSetDevice(c->device));

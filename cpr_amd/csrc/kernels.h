@@ -109,6 +109,12 @@ int64_t run_episodes_list_bytes(const NakParams& P, int32_t mode, bool recs, int
 int run_episodes_fusable(const NakParams& P, int32_t mode, bool recs);
 // points per lane: instantiations for 2 .. this (kind 1, kind 2)
 constexpr int kFuseMax = CPR_NAK_FUSE_MAX, kFuseMaxArr = CPR_NAK_FUSE_MAX_ARR;
+// lanes per episode (nak_fused.h "lane groups"): powers of two 2 .. this, full lanes only
+constexpr int kFuseLanes = CPR_NAK_FUSE_LANES, kFuseLanesArr = CPR_NAK_FUSE_LANES_ARR;
+// the most points one launch runs
+constexpr int kFusePoints = kFuseMax * kFuseLanes > kFuseMaxArr * kFuseLanesArr
+                                ? kFuseMax * kFuseLanes
+                                : kFuseMaxArr * kFuseLanesArr;
 // what one point of a fused launch brings of its own (redo entries carry its launch_id; ovf:
 // its overflow flags; both unused when the launch has no redo queue; list: kind 2, its
 // second-pass list of run_episodes_list_bytes)
@@ -122,10 +128,13 @@ struct FusePoint {
 // na in 2 .. kFuseMax points of P (P.t_att is not read), each over episodes first .. first +
 // n_eps - 1; P.next as in launch_run_episodes. Kind 2: the caller then runs every point's
 // eager second pass (launch_run_episodes_second) behind this kernel
+// g lanes per episode (1; or a built lane group with na = the kind's largest): pts holds
+// na * g points, lane j of a group runs points j * na .. j * na + na - 1, and `lanes` covers g
+// lanes per episode
 hipError_t launch_run_episodes_fused(const NakParams& P, uint64_t seed, uint64_t first,
-                                     int64_t n_eps, const FusePoint* pts, int na, int64_t lanes,
-                                     int64_t* redo, uint32_t* redo_n, int64_t redo_cap,
-                                     hipStream_t st);
+                                     int64_t n_eps, const FusePoint* pts, int na, int g,
+                                     int64_t lanes, int64_t* redo, uint32_t* redo_n,
+                                     int64_t redo_cap, hipStream_t st);
 // the eager second pass over one list (the deferred-race launch's second kernel, static grid
 // stride over the listed episodes; launch_run_episodes runs its own through this). On a
 // stream other than the main kernel's it gets neither spill nor tie-replay scratch
@@ -135,7 +144,7 @@ hipError_t launch_run_episodes_second(const NakParams& P, uint64_t seed, uint64_
                                       uint32_t launch_id, int64_t redo_cap, uint8_t* ovf,
                                       hipStream_t st, double* spill = nullptr,
                                       uint8_t* replay = nullptr);
-int run_episodes_fused_blocks_per_cu(const NakParams& P, int na);
+int run_episodes_fused_blocks_per_cu(const NakParams& P, int na, int g = 1);
 // the same fused kernel drawing from a device copy of a cpr_trace (cpr_replay)
 hipError_t launch_replay_episodes(const NakParams& P, const TraceSource& src, int64_t n_eps,
                                   int32_t mode, int64_t activations, double* spill,

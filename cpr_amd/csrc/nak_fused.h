@@ -9,7 +9,10 @@
 // point keeps only its own NakLane. The loops over the points have a compile-time trip count
 // and are unrolled in full: the states stay in registers and no array of lanes is indexed
 // dynamically.
-// Compiles for the host like nakamoto_lane.h (tests/native_fused runs it beside single lanes).
+// Lane groups (below): the lanes of a wave that run further points of the same episode compute
+// one block per G activations each and pass them round in registers.
+// Compiles for the host like nakamoto_lane.h (tests/native_fused and tests/native_lane_groups
+// run it beside single lanes).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,6 +30,14 @@
 // which measured no faster than two (DESIGN.md "Sweep points in one lane")
 #ifndef CPR_NAK_FUSE_MAX_ARR
 #define CPR_NAK_FUSE_MAX_ARR 2
+#endif
+// the largest lane group (lanes that share an episode and its TAG_ACT blocks, below) a kernel
+// with full lanes is built for, per kind: powers of two 2 .. this; 1: none
+#ifndef CPR_NAK_FUSE_LANES
+#define CPR_NAK_FUSE_LANES 2
+#endif
+#ifndef CPR_NAK_FUSE_LANES_ARR
+#define CPR_NAK_FUSE_LANES_ARR 4
 #endif
 
 namespace cpr {
@@ -77,12 +88,12 @@ __host__ __device__ inline CPR_AI void fused_lazy_check(NakLane (&L)[NA], const 
   }
 }
 
-// the next activation of every point: one counter block, NA miners
+// the next activation of every point from its counter block w: one block, NA miners
 template <int NA, int ARR, class St>
-__host__ __device__ inline CPR_AI void fused_activate(NakLane (&L)[NA], const NakParams& P,
-                                                      const St& S, const LaneMem& M,
-                                                      const uint64_t (&t_att)[NA]) {
-  const Words4 w = S.block((uint32_t)L[0].k, TAG_ACT);
+__host__ __device__ inline CPR_AI void fused_activate_w(NakLane (&L)[NA], const NakParams& P,
+                                                        const St& S, const LaneMem& M,
+                                                        const uint64_t (&t_att)[NA],
+                                                        const Words4& w) {
   const uint64_t u = ((uint64_t)(w.w2 >> 5) << 26) | (uint64_t)(w.w3 >> 6);  // Stream::act_u
   const uint32_t uh = (uint32_t)(u >> 26);
   // NakLane::activate's skip test
@@ -96,6 +107,13 @@ __host__ __device__ inline CPR_AI void fused_activate(NakLane (&L)[NA], const Na
     dr.miner = miner_from_words(w.w0, w.w1, t_att[i], 2);
     L[i].template activate<St, ARR ? 2 : 1, false>(P, S, M, dr);
   }
+}
+
+template <int NA, int ARR, class St>
+__host__ __device__ inline CPR_AI void fused_activate(NakLane (&L)[NA], const NakParams& P,
+                                                      const St& S, const LaneMem& M,
+                                                      const uint64_t (&t_att)[NA]) {
+  fused_activate_w<NA, ARR>(L, P, S, M, t_att, S.block((uint32_t)L[0].k, TAG_ACT));
 }
 
 // reset of every point: up to the attacker's first interaction
@@ -162,22 +180,95 @@ __host__ __device__ inline CPR_AI void fused_verify_races(NakLane (&L)[NA], cons
   fused_races_settle<NA>(L, M);
 }
 
-// one gym step of every point with the built-in policy POL (run_gym's loop body)
+// one gym step of every point with the built-in policy POL (run_gym's loop body), in two
+// halves around the activation's counter block: up to the races' list ...
 template <int POL, int NA, int ARR, class St>
-__host__ __device__ inline CPR_AI void fused_step(NakLane (&L)[NA], const NakParams& P,
-                                                  const St& S, const LaneMem& M,
-                                                  const uint64_t (&t_att)[NA]) {
+__host__ __device__ inline CPR_AI void fused_step_pre(NakLane (&L)[NA], const NakParams& P,
+                                                      const St& S, const LaneMem& M) {
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
     L[i].apply(L[i].template policy_action<POL>(P));
     L[i].template resolve<St, 0, ARR ? 2 : 1>(P, S, M);
   }
   if constexpr (ARR != 0) fused_enqueue_races<NA>(L, M);
-  fused_activate<NA, ARR>(L, P, S, M, t_att);
+}
+// ... and the activation from block w on
+template <int NA, int ARR, class St>
+__host__ __device__ inline CPR_AI void fused_step_post(NakLane (&L)[NA], const NakParams& P,
+                                                       const St& S, const LaneMem& M,
+                                                       const uint64_t (&t_att)[NA],
+                                                       const Words4& w) {
+  fused_activate_w<NA, ARR>(L, P, S, M, t_att, w);
   if constexpr (ARR != 0) {
     // the lanes of the wave verify together once the wave's list is nearly full
     if (fused_races_due<NA>(L, M)) fused_verify_races<NA>(L, P, S, M);
   }
 }
+template <int POL, int NA, int ARR, class St>
+__host__ __device__ inline CPR_AI void fused_step(NakLane (&L)[NA], const NakParams& P,
+                                                  const St& S, const LaneMem& M,
+                                                  const uint64_t (&t_att)[NA]) {
+  fused_step_pre<POL, NA, ARR>(L, P, S, M);
+  fused_step_post<NA, ARR>(L, P, S, M, t_att, S.block((uint32_t)L[0].k, TAG_ACT));
+}
+
+// ---- lane groups: G adjacent lanes of a wave (aligned: lanes g0 .. g0 + G - 1, g0 a multiple
+// of G) run the same episode, each with NA points of its own. The TAG_ACT block of an
+// activation is the same for all of them, so each lane computes one block per G activations
+// and the group passes them round: whenever the activation count k (the same in every lane
+// of a wave) is a multiple of G, lane g of the group computes the block of activation k + g
+// into `held`; at activation k every lane takes the block lane k mod G holds. Blocks past
+// the episode's last activation are computed for nothing. The exchange runs at the top of
+// an activation, where the wave is converged; the lanes of a group share their episode
+// index, so they enter and leave the episode loop together and no exchange reads a lane
+// that is not there.
+
+// the held block of lane g of a group at activation count k
+template <int G, class St>
+__host__ __device__ inline CPR_AI void group_fill(Words4& held, const St& S, uint32_t k,
+                                                  int32_t g) {
+  if ((k & (uint32_t)(G - 1)) == 0u) held = S.block(k + (uint32_t)g, TAG_ACT);
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// The exchange: ds_bpermute_b32 from lane g0 + k mod G, four LDS-pipe operations and no
+// VALU. Two DPP forms (a quad_perm broadcast with a rotate of the held blocks; an immediate
+// quad_perm broadcast chosen by a scalar branch on k mod G) measured the same and were
+// taken out again (DESIGN.md "Lane groups").
+// k: the activation count, wave-uniform (in a scalar register); lane: the lane in its wave
+template <int G>
+__device__ inline CPR_AI Words4 group_take(const Words4& held, uint32_t k, int32_t lane) {
+  static_assert(G == 2 || G == 4 || G == 8, "lane groups of 2, 4 or 8");
+  const uint32_t r = k & (uint32_t)(G - 1);
+  const int src = (int)((((uint32_t)lane & ~(uint32_t)(G - 1)) | r) << 2);
+  Words4 w;
+  w.w0 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)held.w0);
+  w.w1 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)held.w1);
+  w.w2 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)held.w2);
+  w.w3 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)held.w3);
+  return w;
+}
+
+// the block of the lane's next activation (G = 1: its own)
+template <int G, int NA, class St>
+__device__ inline CPR_AI Words4 group_block(const NakLane (&L)[NA], const St& S, Words4& held,
+                                            int32_t lane) {
+  if constexpr (G == 1) {
+    return S.block((uint32_t)L[0].k, TAG_ACT);
+  } else {
+    const uint32_t k = (uint32_t)__builtin_amdgcn_readfirstlane(L[0].k);
+    group_fill<G>(held, S, k, lane & (G - 1));
+    return group_take<G>(held, k, lane);
+  }
+}
+#else
+// the host pass over the kernel's body only needs the name (tests/native_lane_groups models
+// a group with group_fill and an exchange of its own)
+template <int G, int NA, class St>
+__host__ __device__ inline Words4 group_block(const NakLane (&L)[NA], const St& S, Words4&,
+                                              int32_t) {
+  return S.block((uint32_t)L[0].k, TAG_ACT);
+}
+#endif
 
 }  // namespace cpr

@@ -205,17 +205,20 @@ struct TraceSource {
 // one episode of its slowest wave instead of after a fixed share per wave; the lanes of a
 // wave keep consecutive episodes started together, so their activation counts stay equal
 // (the keyed counter and the deferred races' wave list rely on it). Without: the static
-// grid stride
+// grid stride.
+// lpe: the lanes that share an episode (k_run_episodes_fused's lane groups: lpe adjacent
+// lanes, so a wave takes WAVE / lpe episodes at a time); nthreads is then the episodes the
+// grid starts with, its threads / lpe
 __device__ inline __attribute__((always_inline)) int64_t nak_next_episode(
-    unsigned long long* next, int64_t e, int64_t nthreads) {
+    unsigned long long* next, int64_t e, int64_t nthreads, int32_t lpe = 1) {
   if (next == nullptr) return e + nthreads;
   const uint64_t live = __ballot(1);
   const int32_t leader = __builtin_ctzll(live);
   const int32_t lane = (int32_t)(threadIdx.x % WAVE);
   unsigned long long base = 0ull;
-  if (lane == leader) base = atomicAdd(next, (unsigned long long)WAVE);
+  if (lane == leader) base = atomicAdd(next, (unsigned long long)(WAVE / lpe));
   base = __shfl(base, leader);
-  return nthreads + (int64_t)base + lane;
+  return nthreads + (int64_t)base + lane / lpe;
 }
 
 }  // namespace cpr

@@ -423,9 +423,13 @@ class Batch:
         ``ctx.synchronize()``. The launch may be deferred until then: summary-only calls of
         one context on the gym's two-defender networks (gamma <= .5) that share seed, first
         episode and episode count (an alpha sweep with common random numbers) run as one
-        kernel per group of up to five (gamma = 0) or two, with the same results; any other call
-        on the context or its batches launches what is pending first. ``CPR_NAK_FUSE`` (read
-        at every call) is the largest group; 0 launches every call at once."""
+        kernel per group, with the same results: up to five points (gamma = 0) or two in one
+        lane, and two (gamma = 0) or four adjacent lanes that run further points of the same
+        episode and share its draws, so ten or eight calls make one launch; fewer pending
+        calls run in groups of one lane's points. Any other call on the context or its
+        batches launches what is pending first. ``CPR_NAK_FUSE`` (read at every call) is the
+        most points per lane; 0 launches every call at once. ``CPR_NAK_FUSE_LANES`` (read at
+        every call) caps the lanes per episode; 1 keeps the groups of one lane."""
         L.check(
             L.lib().cpr_run_episodes_async(
                 self.handle, n_episodes, first_episode, summary_dev_ptr, records_dev_ptr

@@ -392,12 +392,18 @@ int cpr_run_episodes(cpr_batch* b, int64_t n_episodes, uint64_t first_episode,
  * built-in policy and only max_steps <= 2^14 ending the episode wait in the context's pending
  * group; calls that share seed, first_episode, n_episodes and every parameter but alpha (a
  * sweep with common random numbers) join it and run as one kernel that computes each
- * activation's draws once for all of them (up to five points at gamma = 0, two otherwise);
- * the summaries are the same words as those of separate launches. The group is
- * launched when it is full, before a call that does not join it is handled, and at the
- * start of every other entry point that takes the context or one of its batches. An error of
- * a deferred launch is returned by the call that triggers the launch. CPR_NAK_FUSE (read at
- * every call) gives the largest group; 0 or 1: every call launches at once. */
+ * activation's draws once for all of them (up to five points per lane at gamma = 0, two
+ * otherwise, and adjacent lanes that run further points of the same episode and pass the
+ * draws round: ten points in one launch at gamma = 0, eight otherwise); the summaries are the
+ * same words as those of separate launches. The group is launched when it is full (one full
+ * lane-group launch), before a call that does not join it is handled, and at the start of
+ * every other entry point that takes the context or one of its batches; what is pending is
+ * then cut into full lane-group launches first, the rest into groups of one lane's points,
+ * a single call as its own launch. An error of a deferred launch is returned by the call
+ * that triggers the launch. CPR_NAK_FUSE (read at every call) gives the most points per
+ * lane; 0 or 1: every call launches at once. CPR_NAK_FUSE_LANES (read at every call) caps
+ * the lanes per episode; 1: groups of one lane's points only, launched when those are
+ * full. */
 int cpr_run_episodes_async(cpr_batch* b, int64_t n_episodes, uint64_t first_episode,
                            cpr_summary* summary_dev, cpr_episode_record* records_dev);
 int cpr_synchronize(cpr_ctx* ctx);

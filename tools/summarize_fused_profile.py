@@ -20,7 +20,9 @@ def short(name):
         return None, 0
     args = [a.strip() for a in m.group(2).split(",")]
     if m.group(1):
-        return f"k_run_episodes_fused<{', '.join(args)}>", int(args[1])
+        # <POL, NA, ARR, G>: NA points per lane, G lanes per episode (before lane groups: no G)
+        lanes = int(args[3]) if len(args) > 3 else 1
+        return f"k_run_episodes_fused<{', '.join(args)}>", int(args[1]) * lanes
     return f"k_run_episodes<{', '.join(args)}>", 1
 
 

@@ -73,6 +73,10 @@ POLICY_RANDOM = 5  # loop tasks on the event engine (cpr_protocols.ml:658-782)
 
 PROTO_FC16 = 4  # gym/rust/src/fc16.rs abstract model (fused episodes)
 PROTO_FC16_ENV = 5  # the same model with lockstep lanes: reset / step, networks, the learner
+# gym/rust/src/generic/mod.rs over proto/nakamoto.rs (Nakamoto-v0): release / consider per block
+PROTO_GENERIC_NAKAMOTO = 6
+GENERIC_MAX_STEPS = 4096  # csrc/generic_lane.h kGenericMaxSteps
+GENERIC_MAX_K = 11
 FC16_POLICY_HONEST = 0
 FC16_POLICY_SM1 = 1
 FC16_POLICY_TABLE = 2

@@ -188,6 +188,8 @@ struct cpr_batch {
   fc16::Fc16Params FP;   // CPR_PROTO_FC16, CPR_PROTO_FC16_ENV
   bool is_fc16 = false;  // either of them: the fused-episode kernel k_fc16_episodes
   bool fc16_env = false; // CPR_PROTO_FC16_ENV: lockstep lanes over bk_slots (Fc16Slot)
+  generic::GenericParams GP;  // CPR_PROTO_GENERIC_NAKAMOTO
+  bool gen_env = false;  // its lockstep lanes: headers and block regions pooled in bk_lmem
   bool roll_fused = false;  // the last cpr_rollout_net(_env) ran as k_fc16_rollout_net
   bool is_ev = false;    // B_k or Tailstorm event-engine lanes
   // Nakamoto fused episodes: exact re-runs of flagged episodes on the event engine
@@ -420,6 +422,32 @@ static int validate_fc16(const cpr_config* c, fc16::Fc16Params* P) {
   P->t_term = alpha_threshold(1.0 / c->horizon);
   P->max_steps = c->max_steps > 0 ? c->max_steps : (int64_t)1 << 30;
   P->policy = c->policy;
+  return CPR_OK;
+}
+
+// The generic release/consider env over Nakamoto (gym/rust/src/generic/mod.rs:384-400 Env::new;
+// generic_lane.h). max_steps bounds the lane's block DAG, so it is required.
+static int validate_generic(const cpr_config* c, generic::GenericParams* P) {
+  if (std::isnan(c->alpha) || c->alpha < 0. || c->alpha > 1.)
+    return fail(CPR_E_INVALID_ARG, "alpha < 0 || alpha > 1");
+  if (std::isnan(c->gamma) || c->gamma < 0. || c->gamma > 1.)
+    return fail(CPR_E_INVALID_ARG, "gamma < 0 || gamma > 1");
+  if (!(c->horizon >= 1.)) return fail(CPR_E_INVALID_ARG, "horizon must be >= 1");
+  if (c->mode != CPR_MODE_GYM) return fail(CPR_E_UNSUPPORTED, "the generic env runs gym episodes");
+  if (c->max_steps <= 0)
+    return fail(CPR_E_INVALID_ARG, "generic env: max_steps must be > 0 (it bounds the lane's "
+                                   "block DAG)");
+  if (c->max_steps > generic::kGenericMaxSteps)
+    return fail(CPR_E_INVALID_ARG, "generic env: max_steps above the built cap of " +
+                                       std::to_string(generic::kGenericMaxSteps));
+  if (c->k < 1 || c->k > generic::kGenericMaxK)
+    return fail(CPR_E_INVALID_ARG, "generic env: k (release / consider entries of the "
+                                   "network's action head) must be in 1..11");
+  memset(P, 0, sizeof(*P));
+  P->t_alpha = alpha_threshold(c->alpha);
+  P->t_gamma = alpha_threshold(c->gamma);
+  P->t_term = alpha_threshold(1.0 / c->horizon);
+  P->max_steps = (int32_t)c->max_steps;
   return CPR_OK;
 }
 
@@ -856,7 +884,12 @@ int cpr_batch_create(cpr_ctx* ctx, const cpr_config* cfg, cpr_batch** out) {
   fc16::Fc16Params FP;
   memset(&FP, 0, sizeof(FP));
   const bool is_fc16 = cfg->protocol == CPR_PROTO_FC16 || cfg->protocol == CPR_PROTO_FC16_ENV;
-  int rc = is_fc16 ? validate_fc16(cfg, &FP) : validate(cfg, &P, &EP, &BP, &TP);
+  generic::GenericParams GP;
+  memset(&GP, 0, sizeof(GP));
+  const bool gen_env = cfg->protocol == CPR_PROTO_GENERIC_NAKAMOTO;
+  int rc = gen_env   ? validate_generic(cfg, &GP)
+           : is_fc16 ? validate_fc16(cfg, &FP)
+                     : validate(cfg, &P, &EP, &BP, &TP);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   cpr_batch* b = new cpr_batch;
@@ -869,6 +902,8 @@ int cpr_batch_create(cpr_ctx* ctx, const cpr_config* cfg, cpr_batch** out) {
   b->FP = FP;
   b->is_fc16 = is_fc16;
   b->fc16_env = cfg->protocol == CPR_PROTO_FC16_ENV;
+  b->GP = GP;
+  b->gen_env = gen_env;
   b->eth_bytes = eth::eth_lane_bytes(EP.cap_b, EP.cap_e, EP.n);
   if (cfg->protocol == CPR_PROTO_BK) b->bk_bytes = bk::bk_lane_bytes(BP);
   if (cfg->protocol == CPR_PROTO_TAILSTORM) b->bk_bytes = ts::ts_lane_bytes(TP);
@@ -1431,9 +1466,14 @@ static bool rerun_hybrid(const cpr_batch* b, bool trace, NakParams* NP) {
   return hyb;
 }
 
+static const char* kGenericNoFused =
+    "generic env: no built-in policy runs its episodes (no fused kernel); step the lanes "
+    "(cpr_step) or roll out a network (cpr_rollout_net)";
+
 static int run_async(cpr_batch* b, int64_t n, uint64_t first, const TraceSource* tr,
                      cpr_summary* sum_dev, cpr_episode_record* rec_dev) {
   if (b->is_fc16) return run_async_fc16(b, n, first, tr, sum_dev, rec_dev);
+  if (b->gen_env) return fail(CPR_E_UNSUPPORTED, kGenericNoFused);
   if (b->cfg.protocol == CPR_PROTO_ETHEREUM || b->nak_ev)
     return run_async_eth(b, n, first, tr, sum_dev, rec_dev);
   if (b->is_ev) return run_async_bk(b, n, first, tr, sum_dev, rec_dev);
@@ -1698,6 +1738,7 @@ static int fuse_launch_pending(cpr_ctx* c) {
 int cpr_run_episodes_async(cpr_batch* b, int64_t n, uint64_t first, cpr_summary* sum_dev,
                            cpr_episode_record* rec_dev) {
   if (!b || !sum_dev) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  if (b->gen_env) return fail(CPR_E_UNSUPPORTED, kGenericNoFused);
   if (n <= 0) return CPR_OK;
   cpr_ctx* c = b->ctx;
   const int kind = fuse_kind(b, rec_dev);
@@ -1771,6 +1812,7 @@ int cpr_run_episodes(cpr_batch* b, int64_t n, uint64_t first, cpr_summary* summa
                      cpr_episode_record* records, int records_on_device) {
   if (!b || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
+  if (b->gen_env) return fail(CPR_E_UNSUPPORTED, kGenericNoFused);
   if (n <= 0) return CPR_OK;
   HIP_TRY(hipSetDevice(b->ctx->device));
   return run_sync(b, n, first, nullptr, summary, records, records_on_device);
@@ -1866,6 +1908,7 @@ int cpr_replay(cpr_batch* b, const cpr_trace* t, cpr_summary* summary,
   if (!b || !t || !summary) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
   if (b->fc16_env) return fail(CPR_E_UNSUPPORTED, "FC16 episodes have no trace format");
+  if (b->gen_env) return fail(CPR_E_UNSUPPORTED, "generic env episodes have no trace format");
   if (b->cfg.network == CPR_NET_ABSTRACT_GAMMA)
     return fail(CPR_E_UNSUPPORTED, "the abstract-gamma mode has no trace replay");
   if (t->n_episodes <= 0) return CPR_OK;
@@ -1894,6 +1937,8 @@ int cpr_node_outputs(cpr_batch* b, int64_t n, uint64_t first, const cpr_trace* t
   if (!b || !node_activations || !node_rewards) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
   if (b->is_fc16) return fail(CPR_E_UNSUPPORTED, "FC16 episodes have no network nodes");
+  if (b->gen_env)
+    return fail(CPR_E_UNSUPPORTED, "generic env episodes have two parties, no network nodes");
   if (b->cfg.network == CPR_NET_ABSTRACT_GAMMA)
     return fail(CPR_E_UNSUPPORTED, "the abstract-gamma mode has no exact event engine");
   if (n_nodes != network_nodes(b->cfg))
@@ -1987,6 +2032,7 @@ static int obs_len_of(const cpr_config& c) {
     case CPR_PROTO_ETHEREUM: return 10;
     case CPR_PROTO_TAILSTORM: return 10;
     case CPR_PROTO_FC16_ENV: return 3;
+    case CPR_PROTO_GENERIC_NAKAMOTO: return 5;
     default: return 4;
   }
 }
@@ -2031,8 +2077,21 @@ static int ensure_lockstep_fc16(cpr_batch* b) {
   return ensure_common_lockstep(b, obs_len_of(b->cfg));
 }
 
+// CPR_PROTO_GENERIC_NAKAMOTO: one pool of zeroed lane headers and per-lane block regions (the
+// regions keep what the allocator gives: a lane writes every byte before it reads it)
+static int ensure_lockstep_generic(cpr_batch* b) {
+  const int64_t n = b->cfg.n_lanes;
+  if (n <= 0) return fail(CPR_E_STATE, "batch has no lockstep lanes (cfg.n_lanes = 0)");
+  if (!b->bk_lmem.p) {
+    HIP_TRY(b->bk_lmem.ensure(generic_pool_bytes(b->GP, n)));
+    HIP_TRY(hipMemsetAsync(b->bk_lmem.p, 0, generic_header_bytes(n), b->ctx->stream));
+  }
+  return ensure_common_lockstep(b, obs_len_of(b->cfg));
+}
+
 static int ensure_lockstep(cpr_batch* b) {
   if (b->fc16_env) return ensure_lockstep_fc16(b);
+  if (b->gen_env) return ensure_lockstep_generic(b);
   if (b->is_ev || b->is_eth) return ensure_lockstep_bk(b);
   const int64_t n = b->cfg.n_lanes;
   if (n <= 0) return fail(CPR_E_STATE, "batch has no lockstep lanes (cfg.n_lanes = 0)");
@@ -2138,12 +2197,18 @@ static StepBuffers step_buffers(cpr_batch* b) {
 // The device side of one lockstep step, shared by cpr_step and cpr_rollout_net: the
 // protocol's step kernel(s) on the device actions `act`, outputs into sb, on the context's
 // stream; nothing is copied and nothing waits.
-static int launch_lock_step(cpr_batch* b, const int32_t* act, const StepBuffers& sb) {
+// head_actions: `act` holds indices of the network's action head (the generic env maps them to
+// its integer form; every other protocol's actions are head indices anyway)
+static int launch_lock_step(cpr_batch* b, const int32_t* act, const StepBuffers& sb,
+                            bool head_actions = false) {
   const int64_t n = b->cfg.n_lanes;
   hipStream_t st = b->ctx->stream;
   const double* tabs = (const double*)b->tabs_dev.p;
   const uint64_t* lt = lane_thresholds(b);
-  if (b->fc16_env)
+  if (b->gen_env)
+    HIP_TRY(launch_generic_step(b->GP, b->cfg.seed, b->bk_lmem.p, n, act,
+                                head_actions ? b->cfg.k : 0, sb, st, lt));
+  else if (b->fc16_env)
     HIP_TRY(launch_fc16_step(b->FP, b->cfg.seed, b->bk_slots.p, n, act, sb, st, lt));
   else if (b->is_eth)
     HIP_TRY(launch_eth_step(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
@@ -2195,7 +2260,9 @@ static int launch_lock_reset(cpr_batch* b, const uint8_t* dmask, const uint64_t*
     A.out_alpha = out_alpha;
     HIP_TRY(launch_lane_assign(A, n, st));
   }
-  if (b->fc16_env)
+  if (b->gen_env)
+    HIP_TRY(launch_generic_reset(b->GP, b->bk_lmem.p, n, dmask, deps, obs, st, lt));
+  else if (b->fc16_env)
     HIP_TRY(launch_fc16_reset(b->FP, b->cfg.seed, b->bk_slots.p, n, dmask, deps, obs, st, lt));
   else if (b->is_eth)
     HIP_TRY(launch_eth_reset(b->EP, b->cfg.seed, (uint8_t*)b->bk_lmem.p, b->eth_bytes,
@@ -2264,7 +2331,8 @@ int cpr_step(cpr_batch* b, const int32_t* actions, double* obs, double* reward, 
   const int64_t n = b->cfg.n_lanes;
   const int n_act = b->is_eth ? 24 : b->is_ev ? 8 : 4;
   const int ol = obs_len_of(b->cfg);
-  for (int64_t i = 0; i < n; i++)
+  // (the generic env takes the reference's integers and clamps them to +-256, mod.rs:214-220)
+  for (int64_t i = 0; i < n && !b->gen_env; i++)
     if (actions[i] < 0 || actions[i] >= n_act)
       return fail(CPR_E_INVALID_ARG, "Invalid_argument \"index out of bounds\" (action)");
   HIP_TRY(hipSetDevice(b->ctx->device));
@@ -2300,10 +2368,12 @@ int cpr_observe_fields(cpr_batch* b, int32_t* fields) {
   const int64_t n = b->cfg.n_lanes;
   HIP_TRY(hipSetDevice(b->ctx->device));
   hipStream_t st = b->ctx->stream;
-  const size_t per = (size_t)obs_len_of(b->cfg) * 4;
+  const size_t per = (size_t)(b->gen_env ? 7 : obs_len_of(b->cfg)) * 4;
   DevBuf tmp;
   HIP_TRY(tmp.ensure((size_t)n * per));
-  if (b->fc16_env)
+  if (b->gen_env)
+    HIP_TRY(launch_generic_observe_fields(b->GP, b->bk_lmem.p, n, (int32_t*)tmp.p, st));
+  else if (b->fc16_env)
     HIP_TRY(launch_fc16_observe_fields(b->bk_slots.p, n, (int32_t*)tmp.p, st));
   else if (b->is_eth)
     HIP_TRY(launch_eth_observe_fields(b->EP, (uint8_t*)b->bk_lmem.p, b->eth_bytes, b->bk_slots.p,
@@ -2330,6 +2400,9 @@ int cpr_policy_actions(cpr_batch* b, int32_t policy, const double* obs, int64_t 
   if (b->fc16_env)
     return fail(CPR_E_UNSUPPORTED, "FC16 env: the built-in policies read (a, h, fork) in the "
                                    "fused episodes (cpr_run_episodes), not encoded observations");
+  if (b->gen_env)
+    return fail(CPR_E_UNSUPPORTED, "generic env: no built-in policies on encoded observations "
+                                   "(honest play reads cpr_observe_fields)");
   if (b->cfg.protocol == CPR_PROTO_TAILSTORM) {
     if (policy < 0 || policy > CPR_TS_POLICY_TABLE)
       return fail(CPR_E_INVALID_ARG, "unknown policy");
@@ -2416,6 +2489,18 @@ int cpr_observation_spec(cpr_batch* b, int32_t* obs_len, int32_t* n_actions, dou
   if (!b) return fail(CPR_E_INVALID_ARG, "NULL argument");
   CPR_ENTER(b->ctx);
   const double inf = __builtin_inf();
+  if (b->gen_env) {
+    // mod.rs:913-925 with nakamoto.rs:106-112; the head of 1 + 2K actions (cpr_hip.h)
+    if (obs_len) *obs_len = 5;
+    if (n_actions) *n_actions = 1 + 2 * b->cfg.k;
+    const double lo[5] = {0.0, 0.0, 0.0, -1.0, 0.0};
+    const double hi[5] = {(double)__FLT_MAX__, (double)__FLT_MAX__, 1.0, 0.0, 1.0};
+    for (int i = 0; i < 5; i++) {
+      if (low) low[i] = lo[i];
+      if (high) high[i] = hi[i];
+    }
+    return CPR_OK;
+  }
   if (b->is_fc16) {
     // fc16.rs:61-73: (a, h, fork index) each mapped x -> x / (1 + x); at most 4 actions
     if (obs_len) *obs_len = 3;
@@ -2600,6 +2685,9 @@ int cpr_rollout(cpr_batch* b, int64_t n_steps, double* obs, double* reward, uint
   if (b->fc16_env)
     return fail(CPR_E_UNSUPPORTED, "FC16 env: the built-in policies run as fused episodes "
                                    "(cpr_run_episodes); rollouts take a network (cpr_rollout_net)");
+  if (b->gen_env)
+    return fail(CPR_E_UNSUPPORTED, "generic env: no built-in policies; rollouts take a network "
+                                   "(cpr_rollout_net)");
   if (b->env_table)
     return fail(CPR_E_UNSUPPORTED, "cpr_rollout (built-in policies) runs every lane at cfg.alpha; "
                                    "this batch has an alpha table (cpr_lane_env_set)");
@@ -2886,7 +2974,9 @@ int cpr_policy_net_forward(cpr_batch* b, const double* obs, int64_t n, int deter
 static int launch_lane_cursor(cpr_batch* b, const LaneCursor& c) {
   const int64_t n = b->cfg.n_lanes;
   hipStream_t st = b->ctx->stream;
-  if (b->fc16_env)
+  if (b->gen_env)
+    HIP_TRY(launch_generic_cursor(b->bk_lmem.p, n, c, st));
+  else if (b->fc16_env)
     HIP_TRY(launch_fc16_cursor(b->bk_slots.p, n, c, st));
   else if (b->is_eth)
     HIP_TRY(launch_eth_cursor(b->bk_slots.p, n, c, st));
@@ -2921,6 +3011,9 @@ int cpr_lane_env_set(cpr_batch* b, const cpr_lane_env* env) {
     return fail(CPR_E_INVALID_ARG, "lane env: unknown reward_shape");
   if (env->gym_reward == CPR_GYM_REWARD_DENSE_PER_PROGRESS && b->fc16_env)
     return fail(CPR_E_UNSUPPORTED, "lane env: the FC16 model has no progress target "
+                                   "(CPR_GYM_REWARD_DENSE_PER_PROGRESS)");
+  if (env->gym_reward == CPR_GYM_REWARD_DENSE_PER_PROGRESS && b->gen_env)
+    return fail(CPR_E_UNSUPPORTED, "lane env: the generic env has no progress target "
                                    "(CPR_GYM_REWARD_DENSE_PER_PROGRESS)");
   if (env->gym_reward == CPR_GYM_REWARD_DENSE_PER_PROGRESS && !(env->dense_target > 0.0))
     return fail(CPR_E_INVALID_ARG, "lane env: dense_target <= 0");
@@ -3019,6 +3112,13 @@ static int rollout_net_run(cpr_batch* b, int64_t n_steps, int deterministic,
     return fail(CPR_E_UNSUPPORTED, "FC16 runs fused episodes (cpr_run_episodes) only");
   if (!b->has_net) return fail(CPR_E_STATE, "no policy network set (cpr_policy_net_set)");
   if (b->parked) return fail(CPR_E_STATE, "rollout after cpr_eval_net without a reset");
+  if (b->gen_env) {
+    const char* fq = getenv("CPR_FC16_ROLLOUT_FUSED");
+    if (fq && fq[0] != '0')
+      return fail(CPR_E_UNSUPPORTED, "CPR_FC16_ROLLOUT_FUSED: the one-kernel rollout holds an "
+                                     "FC16 slot in registers; the generic env's block DAG does "
+                                     "not fit there");
+  }
   if (n_steps <= 0) return CPR_OK;
   HIP_TRY(hipSetDevice(b->ctx->device));
   int rc = ensure_lockstep(b);
@@ -3200,7 +3300,7 @@ static int rollout_net_run(cpr_batch* b, int64_t n_steps, int deterministic,
       io.value = D.value ? D.value + t * n : nullptr;
       HIP_TRY(launch_policy_forward(b->pn, io, st));
     }
-    rc = launch_lock_step(b, act, sb);
+    rc = launch_lock_step(b, act, sb, true);
     if (rc) return rc;
     C.out_reward = dqn_epsilon ? slot.reward : D.reward ? D.reward + t * n : nullptr;
     C.out_done = dqn_epsilon ? slot.done : D.done ? D.done + t * n : nullptr;
@@ -3418,7 +3518,7 @@ int cpr_eval_net(cpr_batch* b, const cpr_eval_opts* opts, cpr_eval_record* recor
     const int64_t chunk = std::min<int64_t>(every, bound - t);
     for (int64_t k = 0; k < chunk; ++k) {
       HIP_TRY(launch_policy_forward(b->pn, io, st));
-      rc = launch_lock_step(b, io.action, sb);
+      rc = launch_lock_step(b, io.action, sb, true);
       if (rc) return rc;
       HIP_TRY(launch_eval_collect(C, n, st));
       // a finished lane is reset before it is stepped again (its buffers are sized by max_steps)

@@ -10,6 +10,7 @@
 #include "nakamoto_lane.h"
 #include "nak_fused.h"
 #include "fc16_lane.h"
+#include "generic_lane.h"
 #include "policy_net.h"
 #include "summary.h"
 #include "ts_lane.h"
@@ -460,5 +461,23 @@ struct Fc16Roll {
 // that does not fit is refused (hipErrorInvalidValue) and the caller runs the launch sequence
 bool fc16_rollout_net_fits(const PolNet& N);
 hipError_t launch_fc16_rollout_net(const PolNet& N, const Fc16Roll& R, hipStream_t st);
+
+// The generic release/consider env over Nakamoto (CPR_PROTO_GENERIC_NAKAMOTO, generic_lane.h,
+// kernels_generic.hip): pool = generic_pool_bytes(P, n) bytes whose first
+// generic_header_bytes(n) are zeroed once; observations of 5 doubles per lane. head_k > 0:
+// actions index the categorical head of 1 + 2 head_k actions; 0: the reference's integers.
+size_t generic_header_bytes(int64_t n);
+size_t generic_pool_bytes(const generic::GenericParams& P, int64_t n);
+hipError_t launch_generic_reset(const generic::GenericParams& P, void* pool, int64_t n,
+                                const uint8_t* mask, const uint64_t* eps, double* obs,
+                                hipStream_t st, const uint64_t* lane_t = nullptr);
+hipError_t launch_generic_step(const generic::GenericParams& P, uint64_t seed, void* pool,
+                               int64_t n, const int32_t* actions, int32_t head_k,
+                               const StepBuffers& b, hipStream_t st,
+                               const uint64_t* lane_t = nullptr);
+hipError_t launch_generic_observe_fields(const generic::GenericParams& P, void* pool, int64_t n,
+                                         int32_t* f, hipStream_t st);
+hipError_t launch_generic_cursor(const void* pool, int64_t n, const LaneCursor& c,
+                                 hipStream_t st);
 
 }  // namespace cpr

@@ -343,6 +343,8 @@ class Batch:
         self.handle = h
         self.n_lanes = int(config.n_lanes)
         self.obs_len = self.observation_spec()[0]
+        # int32 per lane of observe_fields: the observation's fields, except for the generic env
+        self.n_fields = 7 if config.protocol == L.PROTO_GENERIC_NAKAMOTO else self.obs_len
         self._coverage_warned = False
         self._lane_env = False
         self._n_alpha = 1  # table entries of the lane env: evaluate_net's result count
@@ -493,7 +495,7 @@ class Batch:
         return obs, rew, done.astype(bool), info
 
     def observe_fields(self):
-        f = np.zeros((self.n_lanes, self.obs_len), dtype=np.int32)
+        f = np.zeros((self.n_lanes, self.n_fields), dtype=np.int32)
         L.check(L.lib().cpr_observe_fields(self.handle, L.ptr(f)))
         return f
 

@@ -145,6 +145,108 @@ class FC16SSZwPT(Env):
         return obs[0], float(r[0]), bool(done[0]) and not truncated, truncated, {}
 
 
+def generic_encode_action(a):
+    """generic/mod.rs:236-248 on the integer form (0 Continue, -(i+1) Release(i), +(i+1)
+    Consider(i)): x / (1 + |x|) in float32, as generic_lane.h generic_encode_action."""
+    a = max(-256, min(256, int(a)))
+    x = np.float32(a)
+    return np.float32(x / np.float32(np.float32(1.0) + abs(x))) if a else np.float32(0.0)
+
+
+def generic_decode_action(a):
+    """generic/mod.rs:250-279: a float32 action in [-1, 1] to the integer form (ValueError
+    outside, as the reference asserts), as generic_lane.h generic_decode_action."""
+    a = np.float32(a)
+    if not (a >= np.float32(-1.0)) or not (a <= np.float32(1.0)):
+        raise ValueError(f"invalid action: {a} outside [-1, 1]")
+    if abs(a) == np.float32(1.0):
+        return 256 if a > 0 else -256
+    with np.errstate(divide="ignore", over="ignore"):
+        x = np.float32(-a) / np.float32(a - np.float32(1.0)) if a >= 0 else \
+            a / np.float32(a + np.float32(1.0))
+    r = np.trunc(x)  # f32::round: half away from zero (x - trunc(x) is exact)
+    if abs(np.float32(x - r)) >= np.float32(0.5):
+        r = r + np.copysign(np.float32(1.0), x)
+    return int(max(-256.0, min(256.0, float(r))))
+
+
+def generic_honest_action(fields):
+    """Honest play on one lane's ``Batch.observe_fields`` row: Release(0) while something can
+    be released, else Consider(0) while something can be considered, else Continue."""
+    return -1 if fields[3] > 0 else (1 if fields[4] > 0 else 0)
+
+
+class Generic(Env):
+    """gym/rust/cpr_gym_rs/envs.py Generic over one device lane (CPR_PROTO_GENERIC_NAKAMOTO),
+    with gymnasium's call shape and the reference's surface: ``step([a])`` takes the float
+    action of generic/mod.rs:227 (decoded with ``generic_decode_action``), returns the reward
+    r / alpha / horizon in float32 (mod.rs:551) and the info keys progress, reward_attacker,
+    reward_defender, rewrite and time (mod.rs:542-548). ``max_steps`` truncates an episode
+    (the reference registers Nakamoto-v0 with max_episode_steps = 1000); ``truncated`` is the
+    lane's capacity status. Episode e of the env runs on the keyed stream of (seed, e)."""
+
+    def __init__(self, protocol="nakamoto", alpha=0.25, gamma=0.5, horizon=25, max_steps=1000,
+                 seed=0, ctx=None):
+        from . import _lib as L
+        from . import device
+
+        if protocol != "nakamoto":
+            raise ValueError("Generic: only protocol='nakamoto' runs on the device")
+        cfg, keep = device.make_config(protocol=L.PROTO_GENERIC_NAKAMOTO, alpha=alpha,
+                                       gamma=gamma, horizon=horizon, max_steps=max_steps,
+                                       seed=seed, policy=0, k=1, n_lanes=1)
+        self._capacity = L.ST_CAPACITY
+        self.alpha, self.horizon = np.float32(alpha), np.float32(horizon)
+        self.batch = device.Batch(cfg, ctx=ctx, keep=keep)
+        self.action_space = Box(np.float32([-1.0]), np.float32([1.0]))
+        self.observation_space = Box(self.low(), self.high())
+        self._episode = -1
+
+    def low(self):
+        return np.array(self.batch.observation_spec()[2], dtype=np.float32)
+
+    def high(self):
+        return np.array(self.batch.observation_spec()[3], dtype=np.float32)
+
+    @staticmethod
+    def encode_action_release(i):
+        return float(generic_encode_action(-(int(i) + 1)))
+
+    @staticmethod
+    def encode_action_consider(i):
+        return float(generic_encode_action(int(i) + 1))
+
+    @staticmethod
+    def encode_action_continue():
+        return 0.0
+
+    @staticmethod
+    def describe_action(a):
+        a = generic_decode_action(np.asarray(a, dtype=np.float32).reshape(-1)[0])
+        return "Continue" if a == 0 else (f"Release({-a - 1})" if a < 0 else f"Consider({a - 1})")
+
+    def reset(self, *args, seed=None, options=None):
+        self._episode += 1
+        obs = self.batch.reset(episode_ids=[self._episode])
+        self._sums, self._n_blocks = np.zeros(3), 1
+        return obs[0].astype(np.float32), {}
+
+    def step(self, action):
+        a = generic_decode_action(np.asarray(action, dtype=np.float32).reshape(-1)[0])
+        obs, r, done, info = self.batch.step([a])
+        sums = np.array([info["episode_progress"][0], info["episode_reward_attacker"][0],
+                         info["episode_reward_defender"][0]])
+        d, self._sums = sums - self._sums, sums
+        f = self.batch.observe_fields()[0]
+        truncated = bool(info["status"][0] & self._capacity)
+        out = dict(progress=float(d[0]), reward_attacker=float(d[1]), reward_defender=float(d[2]),
+                   rewrite=int(f[6]), time=int(f[5] > self._n_blocks))
+        self._n_blocks = int(f[5])  # every Continue, also a guarded one, mines one block
+        rew = np.float32(np.float32(np.float32(r[0]) / self.alpha) / self.horizon)
+        return (obs[0].astype(np.float32), float(rew), bool(done[0]) and not truncated, truncated,
+                out)
+
+
 def env_fn(
     protocol="nakamoto",
     protocol_args=None,
@@ -236,6 +338,9 @@ def device_env_fn(
     fc16 = proto.protocol_id == L.PROTO_FC16_ENV
     if fc16 and reward == "dense_per_progress":
         raise ValueError("device_env_fn: the FC16 model has no progress target "
+                         "(dense_per_progress)")
+    if proto.protocol_id == L.PROTO_GENERIC_NAKAMOTO and reward == "dense_per_progress":
+        raise ValueError("device_env_fn: the generic env has no progress target "
                          "(dense_per_progress)")
     if reward not in ("sparse_relative", "sparse_per_progress", "dense_per_progress"):
         raise KeyError(reward)

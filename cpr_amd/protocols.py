@@ -110,3 +110,21 @@ def fc16(horizon=100, unit_observation=True):
     return Protocol("fc16", "FC'16 abstract selfish-mining model with probabilistic termination",
                     "index into [Wait, Adopt, Override if a > h, Match if a >= h]",
                     unit_observation, protocol_id=L.PROTO_FC16_ENV, horizon=horizon)
+
+
+def generic_nakamoto(horizon=25, actions=2, unit_observation=True):
+    """The reference's generic release/consider env over Nakamoto as a lane env
+    (gym/rust/src/generic/mod.rs with proto/nakamoto.rs, Nakamoto-v0;
+    CPR_PROTO_GENERIC_NAKAMOTO) for ``envs.device_env_fn``. ``actions`` = K: the network's
+    head has 1 + 2K actions, Continue, Release(0..K-1), Consider(0..K-1). The observation is
+    the reference's five values whatever ``unit_observation`` says."""
+    horizon = float(horizon)
+    if not horizon >= 1:
+        raise ValueError("horizon must be >= 1")
+    k = int(actions)
+    if not 1 <= k <= L.GENERIC_MAX_K:
+        raise ValueError(f"actions must be in 1..{L.GENERIC_MAX_K}")
+    return Protocol("generic-nakamoto",
+                    "Nakamoto consensus under the generic release/consider attack space",
+                    f"Continue, Release(0..{k - 1}), Consider(0..{k - 1})",
+                    unit_observation, protocol_id=L.PROTO_GENERIC_NAKAMOTO, horizon=horizon, k=k)

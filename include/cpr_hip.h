@@ -64,7 +64,7 @@ enum cpr_protocol {
                              termination, gym/rust/src/fc16.rs FC16SSZwPT: alpha, gamma,
                              horizon, policy = enum cpr_fc16_policy; fused episodes only
                              (cpr_run_episodes); max_steps caps an episode (CPR_ST_CAPACITY) */
-  CPR_PROTO_FC16_ENV = 5   /* the same model as a lockstep env (additive within ABI v11; a new
+  CPR_PROTO_FC16_ENV = 5,  /* the same model as a lockstep env (additive within ABI v11; a new
                              id because CPR_PROTO_FC16 keeps refusing every lockstep entry).
                              cpr_run_episodes as CPR_PROTO_FC16, and with n_lanes > 0:
                              cpr_reset / cpr_step (action = index 0..3 into the offered list
@@ -77,6 +77,30 @@ enum cpr_protocol {
                              CPR_E_UNSUPPORTED: cpr_rollout,
                              cpr_policy_actions, cpr_replay, cpr_node_outputs and
                              CPR_GYM_REWARD_DENSE_PER_PROGRESS (no progress target) */
+  CPR_PROTO_GENERIC_NAKAMOTO = 6 /* the reference's generic release/consider env over Nakamoto,
+                             gym/rust/src/generic/mod.rs with proto/nakamoto.rs (Nakamoto-v0), as
+                             lockstep lanes over a per-lane block DAG (additive within ABI v11;
+                             generic_lane.h). alpha, gamma, horizon as FC16;
+                             max_steps is required (1 .. 4096: a lane holds max_steps + 1
+                             blocks; CPR_E_INVALID_ARG otherwise) and truncates with
+                             CPR_ST_CAPACITY; k in 1..11 sizes the network's action head.
+                             cpr_step takes the reference's integers (mod.rs:214-220): 0
+                             Continue, -(i+1) Release(i), +(i+1) Consider(i), clamped to +-256;
+                             an index past its list acts as the list's last entry, an empty
+                             list as Continue. Network entries (cpr_rollout_net(_env),
+                             cpr_eval_net, cpr_dqn_*, the learner's buffers) use a head of
+                             1 + 2k actions: 0 Continue, 1..k Release(0..k-1), k+1..2k
+                             Consider(0..k-1). Observation: the reference's five f32 widened to
+                             double (a - ca, d - ca, match feasible, encoded last release,
+                             encoded last consider); unit_observation ignored. Reward: the
+                             step's attacker reward on the defenders' chain. Step infos: episode
+                             sums, n_activations = blocks mined + 1, head_height = the
+                             defenders' entry, head_miner -1. cpr_observe_fields: seven int32
+                             (a, d, match feasible, n_release, n_consider, n_blocks, the last
+                             step's rewrites). A lane whose episode is over ignores steps until
+                             its reset. CPR_E_UNSUPPORTED: cpr_run_episodes, cpr_rollout,
+                             cpr_policy_actions, cpr_replay, cpr_node_outputs,
+                             CPR_GYM_REWARD_DENSE_PER_PROGRESS and CPR_FC16_ROLLOUT_FUSED */
 };
 
 /* policies of the FC16 model (fc16_lane.h); a table maps (a, h, fork) to an action name

@@ -27,6 +27,7 @@ let proto_bk = 2l
 let proto_tailstorm = 3l
 let proto_fc16 = 4l
 let proto_fc16_env = 5l (* the same model with lockstep lanes (added within ABI v11) *)
+let proto_generic_nakamoto = 6l (* generic/mod.rs release/consider env over Nakamoto (within v11) *)
 let net_selfish_mining = 0l
 let net_two_agents = 1l
 let net_honest_clique = 2l

@@ -104,7 +104,9 @@ __global__ __launch_bounds__(kBlock) void k_run_episodes_fused(NakParams P, Seed
   uint64_t t_att[NA];
 #pragma unroll
   for (int i = 0; i < NA; ++i) t_att[i] = own(i, [](const FusePoint& p) { return p.t_att; });
-  NakLane L[NA];
+  // tips packed into one word each (nakamoto_lane.h PTip): no block times here, and
+  // lazy_clock_ok keeps every height and count below 2^16
+  NakLanePacked L[NA];
   Words4 held{0u, 0u, 0u, 0u};  // G > 1: the block this lane computed for its group
   // a wave runs WAVE / G consecutive episodes, its grid nthreads / G
   for (int64_t e = tid / G; e < n_eps; e = nak_next_episode(P.next, e, nthreads / G, G)) {

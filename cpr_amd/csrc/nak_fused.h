@@ -11,6 +11,8 @@
 // dynamically.
 // Lane groups (below): the lanes of a wave that run further points of the same episode compute
 // one block per G activations each and pass them round in registers.
+// The functions are generic over the lane type LN: NakLane, or NakLanePacked as the kernel
+// runs them (tests/native_tips runs the two side by side).
 // Compiles for the host like nakamoto_lane.h (tests/native_fused and tests/native_lane_groups
 // run it beside single lanes).
 #pragma once
@@ -25,9 +27,10 @@
 #ifndef CPR_NAK_FUSE_MAX
 #define CPR_NAK_FUSE_MAX 5
 #endif
-// the same for the deferred-race kernel (gamma = .5), whose points hold more state: 121
-// VGPRs at two points (4 waves/SIMD), 149 / 178 / 206 at three to five (3 / 2 / 2 waves),
-// which measured no faster than two (DESIGN.md "Sweep points in one lane")
+// the same for the deferred-race kernel (gamma = .5), whose points hold more state: with
+// whole tips 121 VGPRs at two points (4 waves/SIMD), 149 / 178 / 206 at three to five (3 / 2 /
+// 2 waves), which measured no faster than two (DESIGN.md "Sweep points in one lane"); with
+// packed tips 109 at two and 130 at three, still 3 waves (DESIGN.md "Packed tips")
 #ifndef CPR_NAK_FUSE_MAX_ARR
 #define CPR_NAK_FUSE_MAX_ARR 2
 #endif
@@ -49,8 +52,8 @@ namespace cpr {
 // sums, the sums (tp, tn: functions of the stream and the activation count) taken once.
 // d = 2; ARR = 0 (gamma = 0): the previous window's only message is its defender block
 // (always inlined: a call would take the lanes' address and put them in scratch memory)
-template <int NA, int ARR, class St>
-__host__ __device__ inline CPR_AI void fused_lazy_check(NakLane (&L)[NA], const NakParams& P,
+template <int NA, int ARR, class St, class LN>
+__host__ __device__ inline CPR_AI void fused_lazy_check(LN (&L)[NA], const NakParams& P,
                                                         const St& S, uint64_t u) {
   bool wb[NA], wr[NA], any = false;
 #pragma unroll
@@ -89,8 +92,8 @@ __host__ __device__ inline CPR_AI void fused_lazy_check(NakLane (&L)[NA], const 
 }
 
 // the next activation of every point from its counter block w: one block, NA miners
-template <int NA, int ARR, class St>
-__host__ __device__ inline CPR_AI void fused_activate_w(NakLane (&L)[NA], const NakParams& P,
+template <int NA, int ARR, class St, class LN>
+__host__ __device__ inline CPR_AI void fused_activate_w(LN (&L)[NA], const NakParams& P,
                                                         const St& S, const LaneMem& M,
                                                         const uint64_t (&t_att)[NA],
                                                         const Words4& w) {
@@ -98,10 +101,10 @@ __host__ __device__ inline CPR_AI void fused_activate_w(NakLane (&L)[NA], const 
   const uint32_t uh = (uint32_t)(u >> 26);
   // NakLane::activate's skip test
   if ((uh - 1u) >= (lazy_hi(P.u_lazy) - 1u) || L[0].tinf) fused_lazy_check<NA, ARR>(L, P, S, u);
-  if constexpr (ARR != 0) L[0].esum += NakLane::lz_term(u);
+  if constexpr (ARR != 0) L[0].esum += LN::lz_term(u);
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
-    NakLane::Draw dr;
+    typename LN::Draw dr;
     dr.dt = 0.0;
     dr.u = u;
     dr.miner = miner_from_words(w.w0, w.w1, t_att[i], 2);
@@ -109,16 +112,16 @@ __host__ __device__ inline CPR_AI void fused_activate_w(NakLane (&L)[NA], const 
   }
 }
 
-template <int NA, int ARR, class St>
-__host__ __device__ inline CPR_AI void fused_activate(NakLane (&L)[NA], const NakParams& P,
+template <int NA, int ARR, class St, class LN>
+__host__ __device__ inline CPR_AI void fused_activate(LN (&L)[NA], const NakParams& P,
                                                       const St& S, const LaneMem& M,
                                                       const uint64_t (&t_att)[NA]) {
   fused_activate_w<NA, ARR>(L, P, S, M, t_att, S.block((uint32_t)L[0].k, TAG_ACT));
 }
 
 // reset of every point: up to the attacker's first interaction
-template <int NA, int ARR, class St>
-__host__ __device__ inline CPR_AI void fused_reset(NakLane (&L)[NA], const NakParams& P,
+template <int NA, int ARR, class St, class LN>
+__host__ __device__ inline CPR_AI void fused_reset(LN (&L)[NA], const NakParams& P,
                                                    const St& S, const LaneMem& M,
                                                    const uint64_t (&t_att)[NA]) {
 #pragma unroll
@@ -131,8 +134,8 @@ __host__ __device__ inline CPR_AI void fused_reset(NakLane (&L)[NA], const NakPa
 // flag word of a lane holds two bits per point (races_check<.., NP>)
 
 // enqueue_race for every point, in point order
-template <int NA>
-__host__ __device__ inline CPR_AI void fused_enqueue_races(NakLane (&L)[NA], const LaneMem& M) {
+template <int NA, class LN>
+__host__ __device__ inline CPR_AI void fused_enqueue_races(LN (&L)[NA], const LaneMem& M) {
   int32_t qn = L[0].qn;
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
@@ -153,13 +156,13 @@ __host__ __device__ inline CPR_AI void fused_enqueue_races(NakLane (&L)[NA], con
 }
 
 // the list must be verified before the next iteration's NA races per lane could overflow it
-template <int NA>
-__host__ __device__ inline CPR_AI bool fused_races_due(const NakLane (&L)[NA], const LaneMem& M) {
+template <int NA, class LN>
+__host__ __device__ inline CPR_AI bool fused_races_due(const LN (&L)[NA], const LaneMem& M) {
   return L[0].qn > M.rq_cap - NA * M.wave;
 }
 
-template <int NA>
-__host__ __device__ inline CPR_AI void fused_races_settle(NakLane (&L)[NA], const LaneMem& M) {
+template <int NA, class LN>
+__host__ __device__ inline CPR_AI void fused_races_settle(LN (&L)[NA], const LaneMem& M) {
   const int32_t fl = M.rflag[M.lane];
   M.rflag[M.lane] = 0;
   L[0].qn = 0;
@@ -170,20 +173,20 @@ __host__ __device__ inline CPR_AI void fused_races_settle(NakLane (&L)[NA], cons
   }
 }
 
-template <int NA, class St>
-__host__ __device__ inline CPR_AI void fused_verify_races(NakLane (&L)[NA], const NakParams& P,
+template <int NA, class St, class LN>
+__host__ __device__ inline CPR_AI void fused_verify_races(LN (&L)[NA], const NakParams& P,
                                                           const St& S, const LaneMem& M) {
   races_publish(S, M);
   wave_lds_order();
-  races_check<St, 2, NA>(L[0], P, S, M);
+  races_check<St, 2, NA, LN>(L[0], P, S, M);
   wave_lds_order();
   fused_races_settle<NA>(L, M);
 }
 
 // one gym step of every point with the built-in policy POL (run_gym's loop body), in two
 // halves around the activation's counter block: up to the races' list ...
-template <int POL, int NA, int ARR, class St>
-__host__ __device__ inline CPR_AI void fused_step_pre(NakLane (&L)[NA], const NakParams& P,
+template <int POL, int NA, int ARR, class St, class LN>
+__host__ __device__ inline CPR_AI void fused_step_pre(LN (&L)[NA], const NakParams& P,
                                                       const St& S, const LaneMem& M) {
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
@@ -193,8 +196,8 @@ __host__ __device__ inline CPR_AI void fused_step_pre(NakLane (&L)[NA], const Na
   if constexpr (ARR != 0) fused_enqueue_races<NA>(L, M);
 }
 // ... and the activation from block w on
-template <int NA, int ARR, class St>
-__host__ __device__ inline CPR_AI void fused_step_post(NakLane (&L)[NA], const NakParams& P,
+template <int NA, int ARR, class St, class LN>
+__host__ __device__ inline CPR_AI void fused_step_post(LN (&L)[NA], const NakParams& P,
                                                        const St& S, const LaneMem& M,
                                                        const uint64_t (&t_att)[NA],
                                                        const Words4& w) {
@@ -204,8 +207,8 @@ __host__ __device__ inline CPR_AI void fused_step_post(NakLane (&L)[NA], const N
     if (fused_races_due<NA>(L, M)) fused_verify_races<NA>(L, P, S, M);
   }
 }
-template <int POL, int NA, int ARR, class St>
-__host__ __device__ inline CPR_AI void fused_step(NakLane (&L)[NA], const NakParams& P,
+template <int POL, int NA, int ARR, class St, class LN>
+__host__ __device__ inline CPR_AI void fused_step(LN (&L)[NA], const NakParams& P,
                                                   const St& S, const LaneMem& M,
                                                   const uint64_t (&t_att)[NA]) {
   fused_step_pre<POL, NA, ARR>(L, P, S, M);
@@ -250,8 +253,8 @@ __device__ inline CPR_AI Words4 group_take(const Words4& held, uint32_t k, int32
 }
 
 // the block of the lane's next activation (G = 1: its own)
-template <int G, int NA, class St>
-__device__ inline CPR_AI Words4 group_block(const NakLane (&L)[NA], const St& S, Words4& held,
+template <int G, int NA, class St, class LN>
+__device__ inline CPR_AI Words4 group_block(const LN (&L)[NA], const St& S, Words4& held,
                                             int32_t lane) {
   if constexpr (G == 1) {
     return S.block((uint32_t)L[0].k, TAG_ACT);
@@ -264,8 +267,8 @@ __device__ inline CPR_AI Words4 group_block(const NakLane (&L)[NA], const St& S,
 #else
 // the host pass over the kernel's body only needs the name (tests/native_lane_groups models
 // a group with group_fill and an exchange of its own)
-template <int G, int NA, class St>
-__host__ __device__ inline Words4 group_block(const NakLane (&L)[NA], const St& S, Words4&,
+template <int G, int NA, class St, class LN>
+__host__ __device__ inline Words4 group_block(const LN (&L)[NA], const St& S, Words4&,
                                               int32_t) {
   return S.block((uint32_t)L[0].k, TAG_ACT);
 }

@@ -24,6 +24,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cassert>
+#include <type_traits>
+
 #include "cpr_stream.h"
 
 #pragma clang fp contract(off)
@@ -158,6 +161,39 @@ __host__ __device__ inline CPR_AI void sel(BRef& dst, bool c, const BRef& src) {
   dst.fork = pick(c, src.fork, dst.fork);
   dst.tm = pick(c, src.tm, dst.tm);
 }
+
+// A tip of the summary-only lazy kernels (no block times, so BRef::tm and BRef::k are dead,
+// and max_steps <= 2^14 by lazy_clock_ok, so every height and attacker count is at most
+// 2^14 + 1): h in the low and ra in the high half of one word. A select of a tip is two
+// selects, h + 1 is w + 1, the chain's block m above p0 is p0.w + m 0x10001, and heights
+// compare in 16 bits on the low half. The fork heights (and the lane's lca_da) are 16-bit
+// values too, so a difference of a height and a fork is one 16-bit subtraction from the
+// word and no half is ever masked out. Only k_run_episodes_fused runs lanes over it.
+// The host build asserts that no h carries into ra.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define CPR_HOST_ASSERT(c) ((void)0)
+#else
+#define CPR_HOST_ASSERT(c) assert(c)
+#endif
+struct PTip {
+  uint32_t w;     // h | ra << 16
+  uint16_t fork;  // as BRef::fork
+};
+__host__ __device__ inline CPR_AI uint16_t tip_h(const PTip& x) { return (uint16_t)x.w; }
+__host__ __device__ inline CPR_AI void sel(PTip& dst, bool c, const PTip& src) {
+  dst.w = pick(c, src.w, dst.w);
+  dst.fork = pick(c, src.fork, dst.fork);
+}
+__host__ __device__ inline CPR_AI BRef tip_unpack(const PTip& x) {
+  BRef r;
+  r.h = (int32_t)(x.w & 0xffffu);
+  r.ra = (int32_t)(x.w >> 16);
+  r.k = 0;  // not kept
+  r.fork = x.fork;
+  r.tm = 0.0;
+  return r;
+}
+__host__ __device__ inline CPR_AI BRef tip_unpack(const BRef& x) { return x; }
 
 struct NakParams {
   uint64_t t_att;       // floor(alpha * 2^32)
@@ -480,7 +516,13 @@ __host__ __device__ inline CPR_AI uint64_t tie_table_d2(const NakParams& P, cons
   return on ? (1ull << (2 - miner)) : 0ull;  // bit j - 1, j = 3 - miner
 }
 
-struct NakLane {
+// Tip: BRef, or PTip for the lanes of k_run_episodes_fused (d = 2, no block times, lazy
+// clock, ties by rule or deferred: what those kernels run and nothing else)
+template <class Tip>
+struct NakLaneT {
+  static constexpr bool PK = std::is_same<Tip, PTip>::value;
+  using Mask = typename std::conditional<PK, uint32_t, uint64_t>::type;
+  using Fork = typename std::conditional<PK, uint16_t, int32_t>::type;  // a fork height
   double t;          // time of the latest activation (clock.now at the interaction)
   int32_t k;         // activations so far (clock.c_activations); the same in every lane of
                      // a wave, so the keyed-stream counter and release keys stay uniform
@@ -494,9 +536,9 @@ struct NakLane {
   int32_t rlo, rhi;  // chain indices released in the current window (shared at count k);
                      // kept until the next activation, whose overlap check reads them
   uint32_t status;
-  BRef p0, pub, D, A, b;
-  uint64_t onA;      // bit j-1: defender j prefers A (else D)
-  int32_t lca_da;    // height of LCA(D, A)
+  Tip p0, pub, D, A, b;
+  Mask onA;          // bit j-1: defender j prefers A (else D) (packed tips: d = 2, one word)
+  Fork lca_da;       // height of LCA(D, A)
   int32_t w_hasb;    // the window resolved last delivered a defender block
   double w_bound;    // conservative bound on that window's latest arrival
   int32_t qn;        // deferred races in the wave's list (TT = 2; the same in every lane)
@@ -517,28 +559,54 @@ struct NakLane {
   }
 
   // chain block m (m >= 1) of the private chain; p0 for m <= 0
-  __host__ __device__ inline CPR_AI BRef chain_ref(const LaneMem& M, int32_t m) const {
-    BRef r;
+  __host__ __device__ inline CPR_AI Tip chain_ref(const LaneMem& M, int32_t m) const {
+    Tip r;
     const bool above = m > 0;
     const int32_t mm = above ? m : 0;
-    r.h = p0.h + mm;
-    r.ra = p0.ra + mm;
-    r.k = pick(above, K_PRIVATE, p0.k);
-    r.fork = r.h;  // p0.fork == p0.h always (apply sets it on Adopt)
-    r.tm = 0.0;  // (chain_t reads the ring and its spill: only for a block that is there)
-    if (M.times) r.tm = above ? chain_t(M, m) : p0.tm;
-    return r;
+    if constexpr (PK) {
+      CPR_HOST_ASSERT((p0.w & 0xffffu) + (uint32_t)mm <= 0xffffu &&
+                      (p0.w >> 16) + (uint32_t)mm <= 0xffffu);
+      // + mm 0x10001, as a shift and an or (mm < 2^16): a multiply costs four times as much
+      r.w = p0.w + (((uint32_t)mm << 16) | (uint32_t)mm);
+      r.fork = (uint16_t)r.w;
+      return r;
+    } else {
+      r.h = p0.h + mm;
+      r.ra = p0.ra + mm;
+      r.k = pick(above, K_PRIVATE, p0.k);
+      r.fork = r.h;  // p0.fork == p0.h always (apply sets it on Adopt)
+      r.tm = 0.0;  // (chain_t reads the ring and its spill: only for a block that is there)
+      if (M.times) r.tm = above ? chain_t(M, m) : p0.tm;
+      return r;
+    }
   }
 
   __host__ __device__ inline CPR_AI void init() {
-    BRef g;
-    g.h = 0; g.ra = 0; g.k = K_GENESIS; g.fork = 0; g.tm = 0.0;
-    p0 = pub = D = A = b = g;
+    if constexpr (PK) {
+      const PTip g{0u, 0};
+      p0 = pub = D = A = b = g;
+    } else {
+      BRef g;
+      g.h = 0; g.ra = 0; g.k = K_GENESIS; g.fork = 0; g.tm = 0.0;
+      p0 = pub = D = A = b = g;
+    }
     t = 0.0;
     k = 0; n = 0; rel = 0; n_ba = 0; pend = -1; wminer = 0; event = 0;
     rlo = 1; rhi = 0; status = 0u; onA = 0ull; lca_da = 0;
     w_hasb = 0; w_bound = -__builtin_inf();
     qn = 0; rw = 0u; tinf = 0; esum = 0u;
+  }
+
+  // the same lane over BRef tips (a packed tip's k is not kept: 0)
+  __host__ __device__ inline CPR_AI NakLaneT<BRef> unpacked() const {
+    NakLaneT<BRef> u;
+    u.t = t; u.k = k; u.n = n; u.rel = rel; u.n_ba = n_ba; u.pend = pend; u.wminer = wminer;
+    u.event = event; u.rlo = rlo; u.rhi = rhi; u.status = status;
+    u.p0 = tip_unpack(p0); u.pub = tip_unpack(pub); u.D = tip_unpack(D); u.A = tip_unpack(A);
+    u.b = tip_unpack(b);
+    u.onA = onA; u.lca_da = lca_da; u.w_hasb = w_hasb; u.w_bound = w_bound;
+    u.qn = qn; u.rw = rw; u.tinf = tinf; u.esum = esum;
+    return u;
   }
 
   // the lane's state without block times (the summary-only kernels' whole state) as
@@ -550,8 +618,9 @@ struct NakLane {
     auto wb = [&](const BRef& r) { w((uint32_t)r.h); w((uint32_t)r.ra); w((uint32_t)r.k); w((uint32_t)r.fork); };
     wd(t); w((uint32_t)k); w((uint32_t)n); w((uint32_t)rel); w((uint32_t)n_ba); w((uint32_t)pend);
     w((uint32_t)wminer); w((uint32_t)event); w((uint32_t)rlo); w((uint32_t)rhi); w(status);
-    wb(p0); wb(pub); wb(D); wb(A); wb(b);
-    w((uint32_t)onA); w((uint32_t)(onA >> 32)); w((uint32_t)lca_da); w((uint32_t)w_hasb);
+    wb(tip_unpack(p0)); wb(tip_unpack(pub)); wb(tip_unpack(D)); wb(tip_unpack(A));
+    wb(tip_unpack(b));
+    w((uint32_t)onA); w((uint32_t)((uint64_t)onA >> 32)); w((uint32_t)lca_da); w((uint32_t)w_hasb);
     wd(w_bound);
   }
 
@@ -700,7 +769,12 @@ struct NakLane {
     rlo = 1;
     rhi = 0;
     // deliver the pending release to the attacker's public model (strict >)
-    sel(pub, pend >= 0 && p0.h + pend > pub.h, chain_ref(M, pend));
+    if constexpr (PK) {
+      const PTip r = chain_ref(M, pend);  // (its height is p0.h + pend where pend >= 0)
+      sel(pub, pend >= 0 && tip_h(r) > tip_h(pub), r);
+    } else {
+      sel(pub, pend >= 0 && p0.h + pend > pub.h, chain_ref(M, pend));
+    }
     const bool att = miner == 0;
     {
       // the attacker's block joins the private chain (selects; only the time ring's stores
@@ -718,25 +792,45 @@ struct NakLane {
       n = pick(att, m, n);
     }
     // the defender block (its fields are meaningless when the attacker mined)
-    const bool par_a = M.d2 ? (((uint32_t)onA >> ((miner - 1) & 31)) & 1u) != 0u
-                            : ((onA >> ((miner - 1) & 63)) & 1ull) != 0ull;
-    b.h = pick(par_a, A.h, D.h) + 1;
-    b.ra = pick(par_a, A.ra, D.ra);
-    b.fork = pick(par_a, A.fork, D.fork);
-    b.k = ka;
-    b.tm = M.times ? tn : 0.0;
-    const bool fresh = !att & (b.h > pub.h);
-    sel(pub, fresh, b);
-    event = pick(att, 0, pick(fresh, 3, 1));
+    if constexpr (PK) {
+      (void)ka;
+      // d = 2: defender j's bit j - 1 is j itself (1, 2), and the attacker (0) has none
+      const bool par_a = (onA & (uint32_t)miner) != 0u;
+      b.w = pick(par_a, A.w, D.w) + 1u;  // h + 1, the parent's ra
+      CPR_HOST_ASSERT((b.w & 0xffffu) != 0u);
+      b.fork = pick(par_a, A.fork, D.fork);
+      const bool fresh = !att & (tip_h(b) > tip_h(pub));
+      sel(pub, fresh, b);
+      event = pick(att, 0, pick(fresh, 3, 1));
+    } else {
+      const bool par_a = M.d2 ? (((uint32_t)onA >> ((miner - 1) & 31)) & 1u) != 0u
+                              : ((onA >> ((miner - 1) & 63)) & 1ull) != 0ull;
+      b.h = pick(par_a, A.h, D.h) + 1;
+      b.ra = pick(par_a, A.ra, D.ra);
+      b.fork = pick(par_a, A.fork, D.fork);
+      b.k = ka;
+      b.tm = M.times ? tn : 0.0;
+      const bool fresh = !att & (b.h > pub.h);
+      sel(pub, fresh, b);
+      event = pick(att, 0, pick(fresh, 3, 1));
+    }
   }
 
   __host__ __device__ inline CPR_AI void observe(int32_t* pub_blocks, int32_t* priv_blocks,
                                           int32_t* diff_blocks, int32_t* ev) const {
-    const int32_t ca = pub.fork;
-    const int32_t ph = p0.h + n;
-    *pub_blocks = pub.h - ca;
-    *priv_blocks = ph - ca;
-    *diff_blocks = ph - pub.h;
+    if constexpr (PK) {
+      const uint32_t ca = pub.fork;
+      // differences of heights in 16 bits: the first two are not negative
+      *pub_blocks = (int32_t)(uint16_t)(pub.w - ca);
+      *priv_blocks = (int32_t)(uint16_t)(p0.w + (uint32_t)n - ca);
+      *diff_blocks = (int32_t)(int16_t)(uint16_t)(p0.w + (uint32_t)n - pub.w);
+    } else {
+      const int32_t ca = pub.fork;
+      const int32_t ph = p0.h + n;
+      *pub_blocks = pub.h - ca;
+      *priv_blocks = ph - ca;
+      *diff_blocks = ph - pub.h;
+    }
     *ev = event & 1;
   }
 
@@ -745,6 +839,41 @@ struct NakLane {
   // Override: release up to the public height (+1); Wait (and any out-of-range action,
   // rejected by the host) shares nothing.
   __host__ __device__ inline CPR_AI void apply(int32_t action) {
+    if constexpr (PK)
+      apply_packed(action);
+    else
+      apply_refs(action);
+  }
+  // packed tips: the same, with the forks' selects on Adopt and `fresh` merged into one on
+  // the combined condition (two selects and a min per fork instead of three)
+  __host__ __device__ inline CPR_AI void apply_packed(int32_t action) {
+    const bool adopt = action == A_ADOPT;
+    const bool relx = action == A_MATCH || action == A_OVERRIDE;
+    const uint16_t hp = tip_h(pub);
+    const bool fresh = (event & 2) != 0;
+    const bool onch = pub.fork == hp;
+    const auto lo = [](int32_t x, int32_t y) { return x < y ? x : y; };
+    const auto lo16 = [](uint16_t x, uint16_t y) { return x < y ? x : y; };
+    const bool af = adopt & fresh, an = adopt & !fresh;
+    const uint16_t hpx = pick(onch, hp, (uint16_t)0xffffu);
+    // pub.h - p0.h, signed, from the low halves
+    int32_t mf = (int32_t)(int16_t)(uint16_t)(pub.w - p0.w) + pick(action == A_OVERRIDE, 1, 0);
+    mf = pick(mf < 0, 0, lo(mf, n));
+    const bool newrel = relx & (mf > rel);
+    rlo = pick(newrel, rel + 1, rlo);
+    rhi = pick(newrel, mf, rhi);
+    rel = pick(adopt, 0, pick(newrel, mf, rel));
+    pend = pick(relx, mf, -1);
+    n_ba = pick(adopt, 0, n);
+    n = pick(adopt, 0, n);
+    b.fork = pick(af, tip_h(b), pick(an, lo16(b.fork, hpx), b.fork));
+    D.fork = pick(an, pick(onch, lo16(D.fork, hp), tip_h(D)), D.fork);
+    A.fork = pick(an, pick(onch, lo16(A.fork, hp), lca_da), A.fork);
+    p0.w = pick(adopt, pub.w, p0.w);
+    p0.fork = pick(adopt, hp, p0.fork);
+    pub.fork = pick(adopt, hp, pub.fork);
+  }
+  __host__ __device__ inline CPR_AI void apply_refs(int32_t action) {
     const bool adopt = action == A_ADOPT;
     const bool relx = action == A_MATCH || action == A_OVERRIDE;
     const int32_t hp = pub.h;
@@ -787,6 +916,51 @@ struct NakLane {
   // batches and flags the episode for an eager re-run when a tie decided otherwise.
   template <class St, int AG = -1, int TT = 0>
   __host__ __device__ inline CPR_AI void resolve(const NakParams& P, const St& S, const LaneMem& M) {
+    if constexpr (PK)
+      resolve_packed<TT>(P, M);
+    else
+      resolve_refs<St, AG, TT>(P, S, M);
+  }
+  // packed tips (d = 2, no abstract gamma): heights compared in 16 bits, the defender masks
+  // one word. TT = 2, or TT = 1 in a kernel without releases (ARR = 0), where no race
+  // exists: one that arose all the same would be left to the exact re-run
+  template <int TT>
+  __host__ __device__ inline CPR_AI void resolve_packed(const NakParams& P, const LaneMem& M) {
+    static_assert(TT == 1 || TT == 2, "ties by rule or deferred");
+    const bool released = rhi >= rlo && P.arrive;
+    const uint32_t all = 3u;
+    const bool dm = wminer != 0;
+    const uint16_t xh = (uint16_t)(tip_h(p0) + rhi);
+    const uint16_t hs = (uint16_t)pick(onA != 0u, A.w, D.w);
+    const uint16_t hb = tip_h(b);
+    const uint16_t lca_new = pick(dm, b.fork, D.fork);
+    const bool newA = released & pick(dm, xh >= hb, xh > hs);
+    const bool race = released & dm & (xh == hb);
+    uint32_t mask = all;
+    if constexpr (TT == 2) {
+      // j = 3 - wminer first reached by the release
+      mask = pick(race, 4u >> (wminer & 3), all);
+      rw = pick(race, (uint32_t)wminer | ((uint32_t)rlo << 2) | ((uint32_t)rhi << 14), rw);
+    } else {
+      status |= pick(race, (uint32_t)(ST_TIE | ST_TIE_UNRESOLVED), 0u);
+    }
+    sel(A, newA, chain_ref(M, rhi));
+    lca_da = pick(newA, lca_new, lca_da);
+    // dm ? (newA ? mask : 0) : (newA ? all : onA), with mask == all where the attacker mined
+    onA = pick(newA, mask, pick(dm, 0u, onA));
+    sel(D, dm, b);
+    double bound = dm ? t + P.delta : -__builtin_inf();
+    if (released) {
+      const double ub = t + (P.dmax - 0.0);
+      bound = ub > bound ? ub : bound;
+    }
+    w_bound = bound;
+    w_hasb = dm ? 1 : 0;
+    wminer = 0;
+  }
+  template <class St, int AG, int TT>
+  __host__ __device__ inline CPR_AI void resolve_refs(const NakParams& P, const St& S,
+                                                      const LaneMem& M) {
     const bool released = rhi >= rlo && P.arrive;
     const uint64_t all = all_mask(P.d);
     const bool dm = wminer != 0;
@@ -861,6 +1035,12 @@ struct NakLane {
   // Ref.winner over [attacker preferred; defender tips 1..d] (engine.ml:195-206,
   // nakamoto.ml:43-48): first maximal height, attacker listed first
   __host__ __device__ inline CPR_AI BRef head(const NakParams& P, const LaneMem& M) const {
+    if constexpr (PK)
+      return unpacked().head(P, M);  // once, at the episode's end
+    else
+      return head_refs(P, M);
+  }
+  __host__ __device__ inline CPR_AI BRef head_refs(const NakParams& P, const LaneMem& M) const {
     BRef best = chain_ref(M, n_ba);
     const uint64_t all = all_mask(P.d);
     const uint64_t mb = wminer ? (1ull << (wminer - 1)) : 0ull;
@@ -895,6 +1075,10 @@ struct NakLane {
     return nak_policy(POL >= 0 ? POL : P.policy, h, a, ev, P.table, P.table_dim);
   }
 };
+
+using NakLane = NakLaneT<BRef>;
+// the lanes of k_run_episodes_fused
+using NakLanePacked = NakLaneT<PTip>;
 
 // TT = 2, after resolve: the lanes whose race was taken as decided append it to the wave's
 // dense list (entry: window time, activation count, rw with the owner lane in bits 26..31),
@@ -952,8 +1136,8 @@ __host__ __device__ inline CPR_AI void races_publish(const St& S, const LaneMem&
 // NP > 1 (LZ = 2, nak_fused.h): the list holds the races of NP sweep points per lane; an
 // entry's y is then the +inf flag (bit 0) and its point (bits 1..), and a lane's flag word
 // holds two bits per point
-template <class St, int LZ = 0, int NP = 1>
-__host__ __device__ inline CPR_AI void races_check(const NakLane& L, const NakParams& P,
+template <class St, int LZ = 0, int NP = 1, class LN = NakLane>
+__host__ __device__ inline CPR_AI void races_check(const LN& L, const NakParams& P,
                                                   const St& S, const LaneMem& M) {
   static_assert(NP == 1 || LZ == 2, "several points per lane: lazy clock only");
   // the entries are spread over the lanes that are here: in the last grid-stride round of

@@ -477,6 +477,53 @@ class DqnStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+MDP_VI_AUTO, MDP_VI_RESIDENT, MDP_VI_GLOBAL = 0, 1, 2  # enum cpr_mdp_vi_path
+MDP_VI_CONVERGED, MDP_VI_MAX_ITER, MDP_VI_NOT_CONVERGED = 0, 1, 2  # enum cpr_mdp_vi_status
+
+
+class MdpC(ctypes.Structure):
+    """cpr_mdp: P points of one topology in the dense padded form, host pointers."""
+
+    _fields_ = [
+        ("S", ctypes.c_int32),
+        ("A", ctypes.c_int32),
+        ("T", ctypes.c_int32),
+        ("P", ctypes.c_int32),
+        ("dst", ctypes.c_void_p),
+        ("used", ctypes.c_void_p),
+        ("valid", ctypes.c_void_p),
+        ("rew", ctypes.c_void_p),
+        ("prg", ctypes.c_void_p),
+        ("prb", ctypes.c_void_p),
+    ]
+
+
+class MdpViOptsC(ctypes.Structure):
+    """cpr_mdp_vi_opts."""
+
+    _fields_ = [
+        ("stop_delta", ctypes.c_double),
+        ("discount", ctypes.c_double),
+        ("max_iter", ctypes.c_int64),
+        ("path", ctypes.c_int32),
+    ]
+
+
+class MdpViResultC(ctypes.Structure):
+    """cpr_mdp_vi_result: the caller's arrays and the two scalars the call fills in."""
+
+    _fields_ = [
+        ("value", ctypes.c_void_p),
+        ("progress", ctypes.c_void_p),
+        ("policy", ctypes.c_void_p),
+        ("iter", ctypes.c_void_p),
+        ("delta", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+        ("path_used", ctypes.c_int32),
+        ("kernel_ms", ctypes.c_double),
+    ]
+
+
 class CTrace(ctypes.Structure):
     _fields_ = [
         ("n_episodes", ctypes.c_int64),
@@ -624,6 +671,8 @@ EXPORTS = [
     "cpr_policy_count",
     "cpr_policy_name",
     "cpr_stream_fill",
+    "cpr_mdp_vi_opts_default",
+    "cpr_mdp_value_iteration",
 ]
 
 
@@ -706,6 +755,8 @@ def _declare(L):
     L.cpr_stream_fill.argtypes = [
         vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int64, vp, vp
     ]
+    L.cpr_mdp_vi_opts_default.argtypes = [P(MdpViOptsC)]
+    L.cpr_mdp_value_iteration.argtypes = [vp, P(MdpC), P(MdpViOptsC), P(MdpViResultC)]
 
 
 def lib():

@@ -17,6 +17,7 @@
 #include "eth_window.h"
 #include "kernels.h"
 #include "lane_env.h"
+#include "mdp_vi.h"
 #include "nak_hybrid.h"
 #include "policy_net.h"
 #include "ppo.h"
@@ -4630,6 +4631,211 @@ int cpr_stream_fill(cpr_ctx* ctx, uint64_t seed, uint64_t ep, uint32_t idx0, uin
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   o.release();
   e.release();
+  return CPR_OK;
+}
+
+
+int cpr_mdp_vi_opts_default(cpr_mdp_vi_opts* opts) {
+  if (!opts) return fail(CPR_E_INVALID_ARG, "opts is NULL");
+  opts->stop_delta = 1e-6;
+  opts->discount = 1.0;
+  opts->max_iter = 0;
+  opts->path = CPR_MDP_VI_AUTO;
+  return CPR_OK;
+}
+
+// the sweep cap of a solve with max_iter == 0: kMdpSweepCap; CPR_MDP_VI_SWEEP_CAP lowers it
+// (tests reach `not converged` in a few thousand sweeps)
+static int64_t mdp_sweep_cap() {
+  if (const char* e = getenv("CPR_MDP_VI_SWEEP_CAP")) {
+    const long long v = atoll(e);
+    if (v >= 1 && v < kMdpSweepCap) return v;
+  }
+  return kMdpSweepCap;
+}
+
+int cpr_mdp_value_iteration(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_vi_opts* opts,
+                            cpr_mdp_vi_result* res) {
+  if (!ctx || !mdp || !opts || !res) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(ctx);
+  // everything is checked before the first allocation or launch; a used slot is checked whether
+  // or not its action is valid (the host solver would read value[dst] of such a slot too)
+  if (mdp->S < 1 || mdp->A < 1 || mdp->T < 1 || mdp->P < 1)
+    return fail(CPR_E_INVALID_ARG, "mdp: S, A, T and P must be at least 1");
+  if (!mdp->dst || !mdp->used || !mdp->valid || !mdp->rew || !mdp->prg || !mdp->prb)
+    return fail(CPR_E_INVALID_ARG, "mdp: NULL array");
+  if (!res->value || !res->progress || !res->policy || !res->iter || !res->delta || !res->status)
+    return fail(CPR_E_INVALID_ARG, "result: NULL array");
+  if (!(opts->discount > 0.0 && opts->discount <= 1.0))
+    return fail(CPR_E_INVALID_ARG, "discount must be in (0, 1]");
+  if (!(opts->stop_delta >= 0.0)) return fail(CPR_E_INVALID_ARG, "stop_delta must be >= 0");
+  if (opts->max_iter < 0) return fail(CPR_E_INVALID_ARG, "max_iter must be >= 0");
+  if (opts->stop_delta == 0.0 && opts->max_iter == 0)
+    return fail(CPR_E_INVALID_ARG, "infinite iteration: stop_delta == 0 and max_iter == 0");
+  if (opts->path < CPR_MDP_VI_AUTO || opts->path > CPR_MDP_VI_GLOBAL)
+    return fail(CPR_E_INVALID_ARG, "path: expected 0 (auto), 1 (resident) or 2 (global)");
+  const int64_t S = mdp->S, A = mdp->A, T = mdp->T, P = mdp->P;
+  const int64_t AT = A * T;  // < 2^62
+  if (AT > ((int64_t)1 << 36) / S || AT * S > ((int64_t)1 << 36) / P)
+    return fail(CPR_E_INVALID_ARG, "mdp: more than 2^36 transition slots over all points");
+  const int64_t slots = AT * S;
+  for (int64_t i = 0; i < slots; ++i) {
+    if (!mdp->used[i]) continue;
+    if (mdp->dst[i] < 0 || mdp->dst[i] >= S)
+      return fail(CPR_E_INVALID_ARG, "mdp: a used slot's dst is outside [0, S)");
+    if (!std::isfinite(mdp->rew[i]) || !std::isfinite(mdp->prg[i]))
+      return fail(CPR_E_INVALID_ARG, "mdp: a used slot's rew or prg is not finite");
+    for (int64_t p = 0; p < P; ++p)
+      if (!std::isfinite(mdp->prb[p * slots + i]))
+        return fail(CPR_E_INVALID_ARG, "mdp: a used slot's prb is not finite");
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  const bool fits = mdp_resident_fits(S);
+  if (opts->path == CPR_MDP_VI_RESIDENT && !fits)
+    return fail(CPR_E_CAPACITY, "path resident: the states do not fit one workgroup's LDS");
+  const bool resident =
+      opts->path == CPR_MDP_VI_RESIDENT ||
+      (opts->path == CPR_MDP_VI_AUTO && fits && mdp_auto_resident(AT * S, P, ctx->cus));
+  const int64_t chunks = (S + kMdpBlock - 1) / kMdpBlock;
+  if (!resident && chunks * P > INT32_MAX)
+    return fail(CPR_E_CAPACITY, "path global: more than 2^31 workgroups per sweep");
+
+  // the kernels' layout: state index fastest, unused slots marked by dst = -1
+  std::vector<int32_t> dst_t, status;
+  std::vector<uint8_t> valid_t;
+  std::vector<double> rew_t, prg_t, prb_t;
+  try {  // no exception may cross the C boundary
+    dst_t.resize((size_t)slots);
+    status.resize((size_t)P);
+    valid_t.resize((size_t)(A * S));
+    rew_t.resize((size_t)slots);
+    prg_t.resize((size_t)slots);
+    prb_t.resize((size_t)(slots * P));
+  } catch (const std::exception&) {
+    return fail(CPR_E_CAPACITY, "mdp: out of host memory for the upload copies");
+  }
+  for (int64_t s = 0; s < S; ++s) {
+    for (int64_t a = 0; a < A; ++a) valid_t[a * S + s] = mdp->valid[s * A + a] ? 1 : 0;
+    for (int64_t j = 0; j < AT; ++j) {
+      const int64_t from = s * AT + j, to = j * S + s;
+      const bool u = mdp->used[from] != 0;  // the kernels load unused slots too: dst -1, zeros
+      dst_t[to] = u ? mdp->dst[from] : -1;
+      rew_t[to] = u ? mdp->rew[from] : 0.0;
+      prg_t[to] = u ? mdp->prg[from] : 0.0;
+      for (int64_t p = 0; p < P; ++p) prb_t[p * slots + to] = u ? mdp->prb[p * slots + from] : 0.0;
+    }
+  }
+  DevBuf d_dst, d_valid, d_rew, d_prg, d_prb, d_val[2], d_pro[2], d_pol, d_status, d_iter, d_delta,
+      d_acc;
+  const size_t vec = (size_t)(P * S) * 8;
+  HIP_TRY(d_dst.ensure((size_t)slots * 4));
+  HIP_TRY(d_valid.ensure((size_t)(A * S)));
+  HIP_TRY(d_rew.ensure((size_t)slots * 8));
+  HIP_TRY(d_prg.ensure((size_t)slots * 8));
+  HIP_TRY(d_prb.ensure((size_t)(slots * P) * 8));
+  for (int i = 0; i < (resident ? 1 : 2); ++i) {
+    HIP_TRY(d_val[i].ensure(vec));
+    HIP_TRY(d_pro[i].ensure(vec));
+    HIP_TRY(hipMemsetAsync(d_val[i].p, 0, vec, ctx->stream));
+    HIP_TRY(hipMemsetAsync(d_pro[i].p, 0, vec, ctx->stream));
+  }
+  HIP_TRY(d_pol.ensure((size_t)(P * S) * 4));
+  HIP_TRY(d_status.ensure((size_t)P * 4));
+  HIP_TRY(d_iter.ensure((size_t)P * 8));
+  HIP_TRY(d_delta.ensure((size_t)P * 8));
+  HIP_TRY(d_acc.ensure((size_t)P * 24));
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(d_dst.p, dst_t.data(), (size_t)slots * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_valid.p, valid_t.data(), (size_t)(A * S), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_rew.p, rew_t.data(), (size_t)slots * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_prg.p, prg_t.data(), (size_t)slots * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_prb.p, prb_t.data(), (size_t)(slots * P) * 8, hipMemcpyHostToDevice,
+                         st));
+  HIP_TRY(hipMemsetAsync(d_status.p, 0xFF, (size_t)P * 4, st));  // kMdpRunning
+  HIP_TRY(hipMemsetAsync(d_iter.p, 0, (size_t)P * 8, st));
+  HIP_TRY(hipMemsetAsync(d_delta.p, 0, (size_t)P * 8, st));
+  HIP_TRY(hipMemsetAsync(d_acc.p, 0, (size_t)P * 24, st));
+
+  MdpDev M{(int32_t)S, (int32_t)A, (int32_t)T, (int32_t)P, (const int32_t*)d_dst.p,
+           (const uint8_t*)d_valid.p, (const double*)d_rew.p, (const double*)d_prg.p,
+           (const double*)d_prb.p};
+  MdpRun R{};
+  R.stop_delta = opts->stop_delta;
+  R.discount = opts->discount;
+  R.max_iter = opts->max_iter;
+  R.cap = mdp_sweep_cap();
+  for (int i = 0; i < 2; ++i) {
+    R.value[i] = (double*)d_val[i].p;
+    R.progress[i] = (double*)d_pro[i].p;
+  }
+  R.policy = (int32_t*)d_pol.p;
+  R.status = (int32_t*)d_status.p;
+  R.iter = (int64_t*)d_iter.p;
+  R.delta = (double*)d_delta.p;
+  R.acc = (unsigned long long*)d_acc.p;
+
+  // every point stops after `limit` sweeps at the latest, so both loops below end: the resident
+  // one after limit / kMdpSweepsPerLaunch + 1 launches, the global one after launch limit + 1
+  // (which records the stop of sweep `limit`)
+  const int64_t limit = opts->max_iter > 0 ? opts->max_iter : R.cap;
+  auto all_stopped = [&]() {
+    for (int32_t v : status)
+      if (v == kMdpRunning) return false;
+    return true;
+  };
+  struct Events {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Events() {
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+    }
+  } ev;
+  HIP_TRY(hipEventCreate(&ev.e0));
+  HIP_TRY(hipEventCreate(&ev.e1));
+  HIP_TRY(hipEventRecord(ev.e0, st));
+  bool done = false;
+  if (resident) {
+    const int64_t launches = limit / kMdpSweepsPerLaunch + 1;
+    for (int64_t l = 0; l < launches && !done; ++l) {
+      HIP_TRY(launch_mdp_resident(M, R, st));
+      HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      done = all_stopped();
+    }
+  } else {
+    for (int64_t k = 1; k <= limit + 1 && !done;) {
+      for (int n = 0; n < kMdpReadbackEvery && k <= limit + 1; ++n, ++k)
+        HIP_TRY(launch_mdp_sweep(M, R, k, st));
+      HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      done = all_stopped();
+    }
+  }
+  HIP_TRY(hipEventRecord(ev.e1, st));
+  if (!done) return fail(CPR_E_INTERNAL, "mdp value iteration: a point outlived its sweep limit");
+
+  HIP_TRY(hipMemcpyAsync(res->iter, d_iter.p, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(res->delta, d_delta.p, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(res->policy, d_pol.p, (size_t)(P * S) * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (resident) {
+    HIP_TRY(hipMemcpyAsync(res->value, d_val[0].p, vec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(res->progress, d_pro[0].p, vec, hipMemcpyDeviceToHost, st));
+  }
+  for (int64_t p = 0; p < P && !resident; ++p) {
+    // the global path left the point's vectors in the buffer its last sweep wrote
+    const int i = (int)(res->iter[p] & 1);
+    HIP_TRY(hipMemcpyAsync(res->value + p * S, (const double*)d_val[i].p + p * S, (size_t)S * 8,
+                           hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(res->progress + p * S, (const double*)d_pro[i].p + p * S,
+                           (size_t)S * 8, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  for (int64_t p = 0; p < P; ++p) res->status[p] = status[(size_t)p];
+  res->path_used = resident ? CPR_MDP_VI_RESIDENT : CPR_MDP_VI_GLOBAL;
+  res->kernel_ms = ms;
   return CPR_OK;
 }
 

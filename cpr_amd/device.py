@@ -67,6 +67,55 @@ class Context:
         )
         return (out, ex) if with_exp else out
 
+    MDP_VI_PATHS = {"auto": L.MDP_VI_AUTO, "resident": L.MDP_VI_RESIDENT,
+                    "global": L.MDP_VI_GLOBAL}
+
+    def mdp_value_iteration(self, dst, used, valid, rew, prg, prb, *, stop_delta, discount=1.0,
+                            max_iter=0, path="auto"):
+        """Value iteration on the device (cpr_mdp_value_iteration) for P points that share one
+        topology in the dense padded form: dst, used, rew, prg [S][A][T], valid [S][A], prb
+        [P][S][A][T] (or [S][A][T] for one point). Returns a dict of value, progress, policy
+        [P][S], iter, delta, status [P], path_used ("resident" / "global") and kernel_ms.
+        Invalid input raises ``CprError`` before anything is launched."""
+        dst = np.asarray(dst)
+        if dst.dtype.kind not in "iu":
+            raise ValueError("dst: expected an integer array")
+        if dst.size and (dst.min() < -2 ** 31 or dst.max() >= 2 ** 31):
+            # a cast would wrap it, perhaps into [0, S); clamp it to a value the library refuses
+            # in a used slot and ignores in a padding slot
+            dst = np.where((dst < 0) | (dst >= 2 ** 31), -1, dst)
+        dst = np.ascontiguousarray(dst, dtype=np.int32)
+        if dst.ndim != 3:
+            raise ValueError("dst: expected [S][A][T]")
+        S, A, T = dst.shape
+        used = np.ascontiguousarray(used, dtype=np.uint8)
+        valid = np.ascontiguousarray(valid, dtype=np.uint8)
+        rew = np.ascontiguousarray(rew, dtype=np.float64)
+        prg = np.ascontiguousarray(prg, dtype=np.float64)
+        prb = np.ascontiguousarray(prb, dtype=np.float64)
+        if prb.ndim == 3:
+            prb = prb[None]
+        if used.shape != dst.shape or rew.shape != dst.shape or prg.shape != dst.shape \
+                or valid.shape != (S, A) or prb.ndim != 4 or prb.shape[1:] != dst.shape:
+            raise ValueError("the arrays' shapes do not agree with dst [S][A][T]")
+        P = prb.shape[0]
+        if path not in self.MDP_VI_PATHS:
+            raise ValueError(f"path: expected one of {sorted(self.MDP_VI_PATHS)}")
+        m = L.MdpC(S, A, T, P, dst.ctypes.data, used.ctypes.data, valid.ctypes.data,
+                   rew.ctypes.data, prg.ctypes.data, prb.ctypes.data)
+        o = L.MdpViOptsC(float(stop_delta), float(discount), int(max_iter),
+                         self.MDP_VI_PATHS[path])
+        out = dict(value=np.zeros((P, S)), progress=np.zeros((P, S)),
+                   policy=np.zeros((P, S), np.int32), iter=np.zeros(P, np.int64),
+                   delta=np.zeros(P), status=np.zeros(P, np.int32))
+        r = L.MdpViResultC(*(out[k].ctypes.data for k in
+                             ("value", "progress", "policy", "iter", "delta", "status")))
+        L.check(L.lib().cpr_mdp_value_iteration(self.handle, ctypes.byref(m), ctypes.byref(o),
+                                                ctypes.byref(r)))
+        out["path_used"] = "resident" if r.path_used == L.MDP_VI_RESIDENT else "global"
+        out["kernel_ms"] = r.kernel_ms
+        return out
+
 
 def default_context():
     dev = int(os.environ.get("LOCAL_RANK", "0"))

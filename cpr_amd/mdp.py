@@ -10,7 +10,8 @@ order, same transition order, same floating-point accumulation order, same first
 tie rule) and turns the policy into the `dim * dim * 2` action table that `CPR_POLICY_TABLE`
 evaluates on the device (`nakamoto_lane.h` `nak_policy`: index `(h * dim + a) * 2 + event`).
 
-Host-side numpy; nothing here runs per step.
+Host-side numpy; nothing here runs per step. The value iteration also runs on the device
+(`value_iteration_device`, `solve_grid`: every point of an alpha x gamma grid in one call).
 """
 
 from collections import deque
@@ -124,9 +125,10 @@ def ptmdp(tab, horizon):
     return out
 
 
-def value_iteration(tab, *, stop_delta, discount=1.0, max_iter=0):
-    """explicit_mdp.py:97-177 vectorised over states: per (state, action) the transitions
-    accumulate in their order, the first action with the strictly best value wins."""
+def pack(tab):
+    """The dense padded arrays of ``tab`` (compile_mdp / ptmdp form) that both solvers read:
+    dst, prb, rew, prg, used [S][A][T] and valid [S][A], A and T the largest action and
+    transition counts; padding slots hold zeros and used = False."""
     n = len(tab)
     n_act = max((len(a) for a in tab), default=0)
     n_tr = max((len(l) for a in tab for l in a), default=0)
@@ -142,6 +144,34 @@ def value_iteration(tab, *, stop_delta, discount=1.0, max_iter=0):
             for j, (d, p, r, g) in enumerate(lst):
                 dst[s, i, j], prb[s, i, j], rew[s, i, j], prg[s, i, j] = d, p, r, g
                 used[s, i, j] = True
+    return dict(dst=dst, prb=prb, rew=rew, prg=prg, valid=valid, used=used)
+
+
+_PACK_KEYS = ("dst", "prb", "rew", "prg", "valid", "used")
+
+
+def _packed(tab):
+    """``tab`` packed, or itself if it is a packed MDP already (a dict of pack's arrays)."""
+    if isinstance(tab, dict):
+        missing = [k for k in _PACK_KEYS if k not in tab]
+        if missing:
+            raise ValueError(f"packed MDP without {missing}")
+        return tab
+    return pack(tab)
+
+
+def value_iteration(tab, *, stop_delta, discount=1.0, max_iter=0):
+    """explicit_mdp.py:97-177 vectorised over states: per (state, action) the transitions
+    accumulate in their order, the first action with the strictly best value wins. ``tab`` may
+    be a packed MDP (``pack``); whatever its padding slots hold is ignored."""
+    m = _packed(tab)
+    used = np.asarray(m["used"], bool)
+    valid = np.asarray(m["valid"], bool)
+    dst = np.where(used, m["dst"], 0)
+    prb = np.where(used, m["prb"], 0.0)
+    rew = np.where(used, m["rew"], 0.0)
+    prg = np.where(used, m["prg"], 0.0)
+    n, n_act, n_tr = dst.shape
     value = np.zeros(n)
     progress = np.zeros(n)
     policy = np.zeros(n, np.int64)
@@ -173,25 +203,104 @@ def value_iteration(tab, *, stop_delta, discount=1.0, max_iter=0):
                 vi_delta=delta)
 
 
-def solve(alpha, gamma, *, maximum_fork_length=20, horizon=100, stop_delta=1e-6):
-    """The SSZ'16 Bitcoin MDP solved for PTO revenue; returns (model, states, vi)."""
+def value_iteration_device(tabs, *, stop_delta, discount=1.0, max_iter=0, path="auto", ctx=None):
+    """``value_iteration`` on the device (``device.Context.mdp_value_iteration``) for one MDP
+    or a list of MDPs that share a topology (everything but the probabilities; ``tab``s or
+    packed MDPs), all solved in one call. Returns one dict per MDP (a single dict for a single
+    MDP) with the host solver's keys, bit for bit its results, plus ``vi_status`` (0 converged,
+    1 stopped at max_iter, 2 not converged at the library's sweep cap), ``vi_path`` and
+    ``vi_kernel_ms`` (the whole call's)."""
+    from . import device
+
+    single = _is_single(tabs)
+    ms = [_packed(tabs)] if single else [_packed(t) for t in tabs]
+    if not ms:
+        raise ValueError("no MDP to solve")
+    first = ms[0]
+    used = np.asarray(first["used"], bool)
+    for m in ms[1:]:
+        if np.shape(m["dst"]) != np.shape(first["dst"]) \
+                or not np.array_equal(np.asarray(m["used"], bool), used) \
+                or not np.array_equal(np.asarray(m["valid"], bool),
+                                      np.asarray(first["valid"], bool)) \
+                or any(not np.array_equal(np.where(used, m[k], 0), np.where(used, first[k], 0))
+                       for k in ("dst", "rew", "prg")):
+            raise ValueError("the MDPs do not share one topology (states, actions, "
+                             "destinations, rewards and progress must agree)")
+    if np.asarray(first["dst"]).size == 0:
+        raise ValueError("an MDP needs at least one state, action slot and transition slot")
+    ctx = ctx or device.default_context()
+    r = ctx.mdp_value_iteration(first["dst"], used, first["valid"], first["rew"], first["prg"],
+                                np.stack([np.asarray(m["prb"], np.float64) for m in ms]),
+                                stop_delta=stop_delta, discount=discount, max_iter=max_iter,
+                                path=path)
+    out = [dict(vi_policy=r["policy"][p].astype(np.int64), vi_value=r["value"][p],
+                vi_progress=r["progress"][p], vi_iter=int(r["iter"][p]),
+                vi_delta=float(r["delta"][p]), vi_status=int(r["status"][p]),
+                vi_path=r["path_used"], vi_kernel_ms=r["kernel_ms"])
+           for p in range(len(ms))]
+    return out[0] if single else out
+
+
+def _nesting(x):
+    """Levels of lists / tuples above the scalars of ``x`` (an empty list counts as one)."""
+    if not isinstance(x, (list, tuple)):
+        return 0
+    return 1 + max((_nesting(e) for e in x), default=0)
+
+
+def _is_single(x):
+    """Whether ``x`` is one MDP and not a list of them, by its shape alone: a packed dict is
+    one MDP; a list or tuple that holds a packed dict is a list of MDPs; otherwise a tab
+    nests four levels (states, actions, transitions, the four fields of a transition; lists
+    or tuples alike) and a list of tabs five. Anything else is refused."""
+    if isinstance(x, dict):
+        return True
+    if not isinstance(x, (list, tuple)):
+        raise ValueError("expected a tab, a packed MDP or a list of them")
+    if any(isinstance(e, dict) for e in x):
+        return False
+    depth = _nesting(x)
+    if depth == 4:
+        return True
+    if depth == 5 or not x:
+        return False
+    raise ValueError("expected a tab (tab[s][i] = [(dst, p, reward, progress), ...]), a packed "
+                     "MDP or a list of them; an MDP without any transition must be packed")
+
+
+def _vi(tab, device, stop_delta):
+    if device:
+        return value_iteration_device(tab, stop_delta=stop_delta)
+    return value_iteration(tab, stop_delta=stop_delta)
+
+
+def solve(alpha, gamma, *, maximum_fork_length=20, horizon=100, stop_delta=1e-6, device=False):
+    """The SSZ'16 Bitcoin MDP solved for PTO revenue; returns (model, states, vi).
+    ``device``: solve on the device (the same result, plus ``vi_status``)."""
     model = BitcoinSM(alpha, gamma, maximum_fork_length)
     states, tab = compile_mdp(model)
-    vi = value_iteration(ptmdp(tab, horizon), stop_delta=stop_delta)
+    vi = _vi(ptmdp(tab, horizon), device, stop_delta)
     return model, states, vi
 
 
-def policy_table(alpha, gamma, *, dim=None, maximum_fork_length=20, horizon=100,
-                 stop_delta=1e-6):
-    """A `CPR_POLICY_TABLE` for `device.make_config(table=...)`: entry (h, a, event) =
-    the MDP's action in state (a, h, IRRELEVANT) for event = ProofOfWork (0) and
-    (a, h, RELEVANT) for event = Network (1) — the attacker's view after its own block or a
-    defender's block; an active match (ACTIVE) is not observable by nakamoto_ssz and shares
-    the ProofOfWork entry. States the MDP does not reach fall back to the other event's entry,
-    else to honest play (nakamoto_ssz.ml:275-284)."""
-    model, states, vi = solve(alpha, gamma, maximum_fork_length=maximum_fork_length,
-                              horizon=horizon, stop_delta=stop_delta)
-    dim = maximum_fork_length + 1 if dim is None else dim
+def solve_grid(alphas, gammas, *, maximum_fork_length=20, horizon=100, stop_delta=1e-6,
+               ctx=None):
+    """``solve`` for every (alpha, gamma), alpha-major, all points in one device call: a list
+    of (model, states, vi), each what ``solve(alpha, gamma)`` returns."""
+    models, all_states, tabs = [], [], []
+    for alpha in alphas:
+        for gamma in gammas:
+            model = BitcoinSM(alpha, gamma, maximum_fork_length)
+            states, tab = compile_mdp(model)
+            models.append(model)
+            all_states.append(states)
+            tabs.append(pack(ptmdp(tab, horizon)))
+    vis = value_iteration_device(tabs, stop_delta=stop_delta, ctx=ctx)
+    return list(zip(models, all_states, vis))
+
+
+def _policy_table_of(model, states, vi, dim):
     act = {}
     for sid, s in enumerate(states):
         acts = model.actions(s)
@@ -209,19 +318,37 @@ def policy_table(alpha, gamma, *, dim=None, maximum_fork_length=20, horizon=100,
     return table.ravel()
 
 
+def policy_table(alpha, gamma, *, dim=None, maximum_fork_length=20, horizon=100,
+                 stop_delta=1e-6, device=False):
+    """A `CPR_POLICY_TABLE` for `device.make_config(table=...)`: entry (h, a, event) =
+    the MDP's action in state (a, h, IRRELEVANT) for event = ProofOfWork (0) and
+    (a, h, RELEVANT) for event = Network (1) — the attacker's view after its own block or a
+    defender's block; an active match (ACTIVE) is not observable by nakamoto_ssz and shares
+    the ProofOfWork entry. States the MDP does not reach fall back to the other event's entry,
+    else to honest play (nakamoto_ssz.ml:275-284). ``device``: solve on the device."""
+    model, states, vi = solve(alpha, gamma, maximum_fork_length=maximum_fork_length,
+                              horizon=horizon, stop_delta=stop_delta, device=device)
+    return _policy_table_of(model, states, vi,
+                            maximum_fork_length + 1 if dim is None else dim)
+
+
+def policy_table_grid(alphas, gammas, *, dim=None, maximum_fork_length=20, horizon=100,
+                      stop_delta=1e-6, ctx=None):
+    """``policy_table`` for every (alpha, gamma), alpha-major, from one ``solve_grid``."""
+    dim = maximum_fork_length + 1 if dim is None else dim
+    return [_policy_table_of(model, states, vi, dim)
+            for model, states, vi in solve_grid(alphas, gammas, horizon=horizon,
+                                                maximum_fork_length=maximum_fork_length,
+                                                stop_delta=stop_delta, ctx=ctx)]
+
+
 # ---- the FC'16 abstract-model kernel (gym/rust/src/fc16.rs, cpr_amd/csrc/fc16_lane.h)
 
 FC16_WAIT, FC16_ADOPT, FC16_OVERRIDE, FC16_MATCH = 0, 1, 2, 3  # fc16.rs:19-25 names
 _FC16_NAME = {WAIT: FC16_WAIT, ADOPT: FC16_ADOPT, OVERRIDE: FC16_OVERRIDE, MATCH: FC16_MATCH}
 
 
-def fc16_table(alpha, gamma, *, dim=None, maximum_fork_length=20, horizon=100,
-               stop_delta=1e-6):
-    """A `CPR_FC16_POLICY_TABLE` (entry (a, h, fork) = an action name) from the solved
-    SSZ'16 MDP: the MDP's action where it defines one, honest play elsewhere."""
-    model, states, vi = solve(alpha, gamma, maximum_fork_length=maximum_fork_length,
-                              horizon=horizon, stop_delta=stop_delta)
-    dim = maximum_fork_length + 1 if dim is None else dim
+def _fc16_table_of(model, states, vi, dim):
     act = {}
     for sid, s in enumerate(states):
         acts = model.actions(s)
@@ -234,6 +361,26 @@ def fc16_table(alpha, gamma, *, dim=None, maximum_fork_length=20, horizon=100,
             for fork in (IRRELEVANT, RELEVANT, ACTIVE):
                 table[a, h, fork] = act.get((a, h, fork), honest)
     return table.ravel()
+
+
+def fc16_table(alpha, gamma, *, dim=None, maximum_fork_length=20, horizon=100,
+               stop_delta=1e-6, device=False):
+    """A `CPR_FC16_POLICY_TABLE` (entry (a, h, fork) = an action name) from the solved
+    SSZ'16 MDP: the MDP's action where it defines one, honest play elsewhere. ``device``:
+    solve on the device."""
+    model, states, vi = solve(alpha, gamma, maximum_fork_length=maximum_fork_length,
+                              horizon=horizon, stop_delta=stop_delta, device=device)
+    return _fc16_table_of(model, states, vi, maximum_fork_length + 1 if dim is None else dim)
+
+
+def fc16_table_grid(alphas, gammas, *, dim=None, maximum_fork_length=20, horizon=100,
+                    stop_delta=1e-6, ctx=None):
+    """``fc16_table`` for every (alpha, gamma), alpha-major, from one ``solve_grid``."""
+    dim = maximum_fork_length + 1 if dim is None else dim
+    return [_fc16_table_of(model, states, vi, dim)
+            for model, states, vi in solve_grid(alphas, gammas, horizon=horizon,
+                                                maximum_fork_length=maximum_fork_length,
+                                                stop_delta=stop_delta, ctx=ctx)]
 
 
 def fc16_action_name(a, h, index):

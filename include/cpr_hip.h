@@ -1011,6 +1011,65 @@ const char* cpr_policy_name(int32_t protocol, int32_t index, int32_t* policy_id)
 int cpr_stream_fill(cpr_ctx* ctx, uint64_t seed, uint64_t episode, uint32_t idx0,
                     uint32_t tag, int64_t n, uint32_t* out, double* exp_out);
 
+/* Value iteration over explicit MDPs (additive within ABI v11; mdp/lib/explicit_mdp.py:97-177
+ * on the device). P points share one topology in the dense padded form: S states,
+ * A action slots per state, T transition slots per action; a point is one probability array.
+ * Host pointers. */
+typedef struct cpr_mdp {
+  int32_t S, A, T, P;
+  const int32_t* dst;   /* [S][A][T] destination state of a used slot */
+  const uint8_t* used;  /* [S][A][T] 0: a padding slot, whatever else it holds is ignored */
+  const uint8_t* valid; /* [S][A]    0: the state does not offer that action */
+  const double* rew;    /* [S][A][T] */
+  const double* prg;    /* [S][A][T] */
+  const double* prb;    /* [P][S][A][T] */
+} cpr_mdp;
+
+enum cpr_mdp_vi_path { CPR_MDP_VI_AUTO = 0, CPR_MDP_VI_RESIDENT = 1, CPR_MDP_VI_GLOBAL = 2 };
+enum cpr_mdp_vi_status {
+  CPR_MDP_VI_CONVERGED = 0,    /* the last sweep's delta <= stop_delta */
+  CPR_MDP_VI_MAX_ITER = 1,     /* stopped after sweep max_iter */
+  CPR_MDP_VI_NOT_CONVERGED = 2 /* max_iter == 0 and the library's sweep cap was reached: 2^20,
+                                  or the lower value of the environment variable
+                                  CPR_MDP_VI_SWEEP_CAP (a test hook) */
+};
+
+typedef struct cpr_mdp_vi_opts {
+  double stop_delta; /* >= 0 */
+  double discount;   /* in (0, 1] */
+  int64_t max_iter;  /* >= 0; 0: until delta <= stop_delta (then stop_delta must be > 0) */
+  int32_t path;      /* enum cpr_mdp_vi_path; AUTO: resident if the states fit one workgroup
+                        and its estimated sweep time is the lower one */
+} cpr_mdp_vi_opts;
+/* stop_delta 1e-6, discount 1, max_iter 0, path AUTO */
+int cpr_mdp_vi_opts_default(cpr_mdp_vi_opts* opts);
+
+typedef struct cpr_mdp_vi_result {
+  double* value;    /* [P][S] */
+  double* progress; /* [P][S] */
+  int32_t* policy;  /* [P][S] the action slot taken, -1 for a state without valid action */
+  int64_t* iter;    /* [P] sweeps done */
+  double* delta;    /* [P] max |value - previous value| of the last sweep */
+  int32_t* status;  /* [P] enum cpr_mdp_vi_status */
+  int32_t path_used; /* CPR_MDP_VI_RESIDENT or CPR_MDP_VI_GLOBAL */
+  double kernel_ms;  /* HIP events around the launches, the status reads between them included */
+} cpr_mdp_vi_result;
+
+/* Per point: value = progress = 0; sweep i computes, per state and valid action in slot order,
+ * this_v += prb (rew + discount value[dst]) and this_p likewise over the used slots in slot
+ * order (f64, one rounding per operation), takes an action when this_v > best_v or none is
+ * taken yet, and gives a state without valid action value 0, progress 0, policy -1. The point
+ * stops after sweep i if max_iter > 0 and i >= max_iter, else if delta <= stop_delta; points
+ * stop independently. Every array of `result` is filled. Checked before anything is launched
+ * (CPR_E_INVALID_ARG): sizes < 1, NULL arrays, a used dst outside [0, S), a non-finite prb, rew
+ * or prg in a used slot, discount outside (0, 1], stop_delta < 0, max_iter < 0, stop_delta == 0
+ * with max_iter == 0, an unknown path. A used slot is checked even under an action with
+ * valid == 0, although no solver takes that action. CPR_E_CAPACITY: no host memory for the
+ * upload copies; path RESIDENT with more states than one
+ * workgroup holds (about 10,000). */
+int cpr_mdp_value_iteration(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_vi_opts* opts,
+                            cpr_mdp_vi_result* result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -404,6 +404,16 @@ let stream_fill =
     @-> ptr double @-> returning int)
 ;;
 
+(* value iteration over explicit MDPs (added within ABI v11): cpr_mdp, cpr_mdp_vi_opts and
+   cpr_mdp_vi_result are untyped pointers to caller-built C structs *)
+let mdp_vi_opts_default = foreign "cpr_mdp_vi_opts_default" (ptr void @-> returning int)
+
+let mdp_value_iteration =
+  foreign
+    "cpr_mdp_value_iteration"
+    (ptr ctx @-> ptr void @-> ptr void @-> ptr void @-> returning int)
+;;
+
 (* errors: every entry point returns a status; non-zero becomes the exception the
    reference raises at the same point (engine.ml:37-51 Failure, network.ml:63-72
    Invalid_argument) *)

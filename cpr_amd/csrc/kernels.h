@@ -245,11 +245,9 @@ hipError_t launch_eth_replay_episodes(const eth::EthParams& P, const TraceSource
                                  cpr_episode_record* recs, cpr_summary* sum, hipStream_t st,
                                    const NodeOut& no = NodeOut());
 int eth_blocks_per_cu();
-// event-heap nodes per lane in the LDS slab of an event-engine kernel launched with
-// `blocks` workgroups (kernels_bk.hip; the B_k and Tailstorm lanes' BkMem / TsMem.hl)
-int32_t ev_slab_nodes(int64_t blocks, const void* kernel);
-// heap slab nodes, visibility-window vertices and dynamic LDS bytes of a B_k / Tailstorm
-// kernel launched with `blocks` workgroups on n nodes (kernels_bk.hip)
+// heap slab nodes (the B_k and Tailstorm lanes' BkMem / TsMem.hl), visibility-window
+// vertices and dynamic LDS bytes of a B_k / Tailstorm kernel launched with `blocks`
+// workgroups on n nodes (ev_plan.hip)
 struct EvSlab {
   int32_t kl, vw;
   size_t bytes;
@@ -310,10 +308,11 @@ size_t eth_slot_bytes();
 // queue aborts it (HSA_STATUS_ERROR_INVALID_ALLOCATION), and HIP reports the abort as "an
 // illegal memory access was encountered" although no memory was accessed
 // (tools/probes/lds_limit_probe.hip, profiles/r6a_lds_probe.log; the round-5 fault of the
-// rejected wave-wide re-run variant). lds_dynamic_max(kernel) = the
-// device's LDS per workgroup less the kernel's static LDS (hipFuncGetAttributes), cached per
-// kernel and device; every launcher that asks for dynamic LDS checks its request with
-// CPR_LDS_GUARD and refuses (hipErrorInvalidValue) rather than dispatch
+// rejected wave-wide re-run variant). lds_dynamic_max(kernel), in
+// ev_plan.hip, = the device's LDS per workgroup less the kernel's static LDS
+// (hipFuncGetAttributes), cached per kernel and device; every launcher that asks for dynamic
+// LDS checks its request with CPR_LDS_GUARD and refuses (hipErrorInvalidValue) rather than
+// dispatch
 int64_t lds_dynamic_max(const void* kernel);
 #define CPR_LDS_GUARD(kernel, dyn)                                          \
   do {                                                                      \

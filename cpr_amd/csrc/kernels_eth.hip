@@ -1,8 +1,13 @@
-// Ethereum episode kernel for gfx950: one lane = one episode of the ethereum_ssz attack
+// Ethereum kernels for gfx950: one lane = one episode / gym env of the ethereum_ssz attack
 // space (gym mode: engine.ml reset/step loop with an on-device policy; loop mode:
 // Simulator.loop ~activations), driven by the exact per-lane event engine of
 // ethereum_lane.h. Each resident lane owns one contiguous HBM region (block ring, node
 // visibility, event heap, scratch) reused for every episode it runs.
+//
+// The event-engine kernels (k_eth_run_episodes, k_eth_reset / k_eth_step, k_eth_rollout,
+// k_eth_observe_fields) are shells around ev_kernels.h's bodies over EthAdapter, shared with
+// kernels_bk.hip and kernels_ts.hip; the window-lane episodes (k_eth_win_episodes), the
+// exact re-runs (k_nak_exact_rerun, k_rerun_overflow) and the policy decode are this unit's.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -13,73 +18,50 @@
 #include "../../include/cpr_hip.h"
 #include "eth_window.h"
 #include "ethereum_lane.h"
-#include "kernels.h"
+#include "ev_kernels.h"
 #include "nak_hybrid.h"
-#include "summary.h"
-#include "wave_sched.h"
 
 #pragma clang fp contract(off)
 
 namespace cpr {
 
+// lockstep gym lanes: engine.ml reset/step with host actions (cpr_reset / cpr_step) and the
+// on-device rollout, one lane region of eth_lane_bytes per env
+struct EthSlot {
+  eth::EthLane L;
+  uint64_t ep;
+  double last_ra;
+  int32_t live;
+};
 
-// one finished episode: summary, record, per-node row
-template <class Src, class St>
-__device__ inline void eth_finish(const eth::EthParams& P, eth::EthLane& L, const eth::EthMem& M,
-                                  const St& S, int64_t e, int32_t hd, Acc& acc, int32_t* hist,
-                                  cpr_episode_record* recs, const NodeOut& no) {
-  L.status |= Src::missed(S);
-  const eth::EBlock& h = L.B(P, M, hd);
-  const int32_t ra = h.rew_att, rd = h.rew_def;
-  const double rel = (ra + rd) != 0 ? (double)ra / (double)(ra + rd) : 0.0;
-  acc_episode(acc, (int64_t)ra << 15, (int64_t)rd << 15, (int64_t)h.work << 20, rel, h.height,
-              L.steps, L.c_act, L.status, hist);
-  if (recs) {
-    cpr_episode_record r;
-    r.reward_attacker = (double)ra / 32.0;
-    r.reward_defender = (double)rd / 32.0;
-    r.progress = (double)h.work;
-    r.chain_time = h.time;
-    r.sim_time = P.mode == CPR_MODE_GYM ? L.now : 0.0;
-    r.n_steps = L.steps;
-    r.n_activations = L.c_act;
-    r.head_height = h.height;
-    r.head_miner = P.mode == CPR_MODE_GYM ? h.miner : -1;
-    r.status = L.status;
-    r.head_work = P.nak ? 0 : h.work;
-    recs[e] = r;
-  }
-  if (no.acts) {  // csv_runner.ml:74-79: sim.activations and (Dag.data head).rewards
-    const int32_t* hr = M.nrew + (int64_t)(hd & (P.cap_b - 1)) * P.n;
-    for (int32_t j = 0; j < P.n; ++j) {
-      no.acts[e * P.n + j] = M.nact[j];
-      no.rews[e * P.n + j] = (double)hr[j] / 32.0;
-    }
-    no.head_miner[e] = h.miner;
-  }
-}
+// ev_kernels.h / wave_sched.h adapter for ethereum_lane.h (also the Nakamoto-mode engine):
+// no LDS slab, every thread a lane, the rollout as a plain loop per lane
+struct EthAdapter : EvAdapterBase<eth::EthLane, eth::EthParams, eth::EthMem> {
+  using Slot = EthSlot;
+  using Obs = eth::EthObs;
+  static constexpr int kObs = 10;
+  static constexpr bool kSlab = false, kRollSched = false;
+  static constexpr int kEvLpw = 64, kRollLpw = 64;
 
-// wave_sched.h adapter for ethereum_lane.h (also the Nakamoto-mode engine)
-struct EthAdapter {
-  using Lane = eth::EthLane;
-  using Par = eth::EthParams;
-  using Mem = eth::EthMem;
-  template <class St>
-  __device__ static void begin(Lane& L, const Par& P, const St& S, const Mem& M) {
-    L.init(P, S, M);
-  }
-  __device__ static bool gym(const Par& P) { return P.mode == CPR_MODE_GYM; }
-  __device__ static bool loop_attacker(const Par& P) { return P.net != 2; }
   __device__ static bool pow0(uint32_t ev) { return (ev & 7u) == eth::EV_DAG && (ev >> 5) == 0u; }
   template <class St>
-  __device__ static void run_pow0(Lane& L, const Par& P, const St&, const Mem& M, int32_t) {
+  __device__ __forceinline__ static void run_pow0(Lane& L, const Par& P, const St&,
+                                                  const Mem& M, int32_t) {
     const eth::Payload d = L.payload(P, M, 0, L.priv, eth::F_MINING, L.own, L.foreign);
     const int32_t v = L.append(P, M, 0, d);
     L.push_now(P, M, eth::mkev(eth::EV_MV, 0, eth::KD_POW), v);
   }
-  __device__ static void act(Lane& L, const Par& P, const Mem& M) {
+  // the lanes' state decides the orphan fields with the three dry-run payloads; the policy
+  // does not read them
+  __device__ __forceinline__ static Obs observe(Lane& L, const Par& P, const Mem& M) {
+    return L.observe(P, M, true);
+  }
+  __device__ __forceinline__ static int32_t policy(Lane& L, const Par& P, const Mem& M) {
     const eth::EthObs o = L.observe(P, M, false);
-    const int32_t sh = L.apply(P, M, eth::lane_action(P, o));
+    return eth::lane_action(P, o);
+  }
+  __device__ static void act(Lane& L, const Par& P, const Mem& M) {
+    const int32_t sh = L.apply(P, M, policy(L, P, M));
     if (sh >= 0) L.share(P, M, 0, sh);
     ++L.steps;
   }
@@ -93,66 +75,89 @@ struct EthAdapter {
     const double progress = (double)L.B(P, M, hd).work;
     return L.dead || !(L.steps < P.max_steps && progress < P.max_progress && L.now < P.max_time);
   }
+
+  __host__ __device__ static int64_t lane_bytes(const Par& P) {
+    return eth::eth_lane_bytes(P.cap_b, P.cap_e, P.n);
+  }
+  __device__ __forceinline__ static Mem mem_at(uint8_t* base, const Par& P) {
+    return eth::eth_mem_at(base, P.cap_b, P.cap_e, P.n);
+  }
+  __device__ __forceinline__ static void node_mem(Mem& M, uint8_t* base, const Par& P) {
+    eth::eth_node_mem(M, base, P.n);
+  }
+
+  // the head's rewards are its int block fields in units of 1/32
+  __device__ __forceinline__ static const eth::EBlock& head_at(Lane& L, const Par& P,
+                                                               const Mem& M, int32_t hd) {
+    return L.B(P, M, hd);
+  }
+  __device__ __forceinline__ static double reward_att(Lane&, const Par&, const Mem&,
+                                                      const eth::EBlock& h) {
+    return (double)h.rew_att / 32.0;
+  }
+  __device__ __forceinline__ static EvHead head(Lane&, const Par& P, const Mem&,
+                                                const eth::EBlock& h) {
+    return {(double)h.rew_att / 32.0,
+            (double)h.rew_def / 32.0,
+            (double)h.work,
+            h.time,
+            h.height,
+            P.mode == CPR_MODE_GYM ? h.miner : -1,
+            P.nak ? 0 : h.work};
+  }
+  __device__ __forceinline__ static int32_t miner(const eth::EBlock& h) { return h.miner; }
+  __device__ __forceinline__ static void acc(Acc& acc, const Par&, Lane& L, const Mem&,
+                                             const eth::EBlock& h, int32_t* hist) {
+    const int32_t ra = h.rew_att, rd = h.rew_def;
+    const double rel = (ra + rd) != 0 ? (double)ra / (double)(ra + rd) : 0.0;
+    acc_episode(acc, (int64_t)ra << 15, (int64_t)rd << 15, (int64_t)h.work << 20, rel, h.height,
+                L.steps, L.c_act, L.status, hist);
+  }
+  __device__ __forceinline__ static auto node_rews(Lane&, const Par& P, const Mem& M, int32_t hd,
+                                                   const eth::EBlock&) {
+    const int32_t* hr = M.nrew + (int64_t)(hd & (P.cap_b - 1)) * P.n;
+    return [hr](int32_t j) { return (double)hr[j] / 32.0; };
+  }
+
+  __device__ __forceinline__ static void fields(const Obs& o, int32_t* g) {
+    g[0] = o.public_height;
+    g[1] = o.public_work;
+    g[2] = o.private_height;
+    g[3] = o.private_work;
+    g[4] = o.diff_height;
+    g[5] = o.diff_work;
+    g[6] = o.public_orphans;
+    g[7] = o.private_orphans_inclusive;
+    g[8] = o.private_orphans_exclusive;
+    g[9] = o.event;
+  }
+  // ethereum_ssz.ml:43-56 normalizers through ssz_tools.ml NormalizeObs.to_float; the unit
+  // encodings use host-tabulated libm values (tabs = [2/pi atan(i) | 0.5 + atan(i - N)/pi],
+  // i < N)
+  __device__ __forceinline__ static void write_obs(const Par&, const Obs& o, int unit,
+                                                   const double* tabs, int32_t tn, double* out) {
+    int32_t v[10];
+    fields(o, v);
+    const double pi = 3.141592653589793;
+    for (int j = 0; j < 10; ++j) {
+      const int32_t x = v[j];
+      if (!unit || j == 9) {
+        out[j] = (double)x;
+      } else if (j == 4 || j == 5) {
+        out[j] = (x > -tn && x < tn) ? tabs[2 * tn + x] : 0.5 + (1.0 / pi * atan((double)x / 1.0));
+      } else {
+        out[j] = x < tn ? tabs[x] : 2.0 / pi * atan((double)x / 1.0);
+      }
+    }
+  }
 };
 
 template <class Src>
 __global__ __launch_bounds__(kBlock) CPR_EV_OCC void k_eth_run_episodes(
-    eth::EthParams P, Src src, int64_t n_eps, uint8_t* mem,
-    int64_t lane_bytes, cpr_episode_record* recs, cpr_summary* sum, NodeOut no) {
-  __shared__ int32_t hist[CPR_HIST_BINS];
-  if (threadIdx.x < CPR_HIST_BINS) hist[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-  eth::EthMem M = eth::eth_mem_at(mem + tid * lane_bytes, P.cap_b, P.cap_e, P.n);
-  if (no.mem) eth::eth_node_mem(M, no.mem + tid * no.lane_bytes, P.n);
-  Acc acc = {};
-  eth::EthLane L;
-#if CPR_EV_SCHED
-  int64_t e = tid;  // wave-coherent dispatch (wave_sched.h), episodes from a work queue
-  auto S = src.at(e < n_eps ? e : 0);
-  EvCursor c;
-  c.cls = -1;
-  c.phase = PH_IDLE;
-  if (e < n_eps) ev_begin<EthAdapter>(L, P, S, M, c);
-  for (;;) {
-    while (c.phase != PH_IDLE && c.cls < 0) {
-      if (c.phase != PH_OVER) ev_fetch<EthAdapter>(L, P, S, M, c);
-      if (c.phase == PH_OVER) {
-        eth_finish<Src>(P, L, M, S, e, c.hd, acc, hist, recs, no);
-        e = ev_next_episode(P.next, e, nthreads);
-        if (e < n_eps) {
-          S = src.at(e);
-          ev_begin<EthAdapter>(L, P, S, M, c);
-        } else {
-          c.phase = PH_IDLE;
-        }
-      }
-    }
-    const int32_t k = ev_choose(c.cls);
-    if (k < 0) break;
-    if (c.cls == k) ev_exec<EthAdapter>(L, P, S, M, c);
-  }
-#else
-  for (int64_t e = tid; e < n_eps; e += nthreads) {
-    const auto S = src.at(e);
-    int32_t hd;
-    if (P.mode == CPR_MODE_GYM) {
-      L.gym_reset(P, S, M);
-      bool done = L.dead != 0;
-      hd = 0;
-      while (!done) {
-        const eth::EthObs o = L.observe(P, M, false);
-        hd = L.gym_step(P, S, M, eth::lane_action(P, o), &done);
-      }
-    } else {
-      hd = L.loop(P, S, M);
-    }
-    eth_finish<Src>(P, L, M, S, e, hd, acc, hist, recs, no);
-  }
-#endif
-  __syncthreads();
-  block_flush(acc, hist, sum);
+    eth::EthParams P, Src src, int64_t n_eps, uint8_t* mem, int64_t lane_bytes,
+    cpr_episode_record* recs, cpr_summary* sum, NodeOut no) {
+  ev_run_episodes_body<EthAdapter, Src>(P, src, n_eps, mem, lane_bytes, recs, sum, no,
+                                        SlabView{nullptr, 0, 0, 0, 0}, EthAdapter::kEvLpw);
 }
 
 // Ethereum gym episodes on the selfish-mining network, a window at a time (eth_window.h):
@@ -541,208 +546,53 @@ hipError_t launch_eth_run_episodes(const eth::EthParams& P, uint64_t seed, uint6
                                    int64_t n_eps, uint8_t* mem, int64_t lane_bytes,
                                    int64_t lanes, cpr_episode_record* recs, cpr_summary* sum,
                                    hipStream_t st, const NodeOut& no) {
-  CPR_LAYOUT_GUARD(lane_bytes, eth::eth_lane_bytes(P.cap_b, P.cap_e, P.n));
-  const unsigned blocks = (unsigned)(lanes / kBlock);
-  hipLaunchKernelGGL(k_eth_run_episodes<SeedSource>, dim3(blocks), dim3(kBlock), 0, st, P,
-                     SeedSource{seed, first}, n_eps, mem, lane_bytes, recs, sum, no);
-  return hipGetLastError();
+  return ev_launch_episodes<EthAdapter>(k_eth_run_episodes<SeedSource>, P,
+                                        SeedSource{seed, first}, n_eps, mem, lane_bytes, lanes,
+                                        recs, sum, st, no);
 }
 
 hipError_t launch_eth_replay_episodes(const eth::EthParams& P, const TraceSource& src, int64_t n_eps,
                                  uint8_t* mem, int64_t lane_bytes, int64_t lanes,
                                  cpr_episode_record* recs, cpr_summary* sum, hipStream_t st,
                                  const NodeOut& no) {
-  CPR_LAYOUT_GUARD(lane_bytes, eth::eth_lane_bytes(P.cap_b, P.cap_e, P.n));
-  hipLaunchKernelGGL(k_eth_run_episodes<TraceSource>, dim3((unsigned)(lanes / kBlock)),
-                     dim3(kBlock), 0, st, P, src, n_eps, mem, lane_bytes, recs, sum, no);
-  return hipGetLastError();
+  return ev_launch_episodes<EthAdapter>(k_eth_run_episodes<TraceSource>, P, src, n_eps, mem,
+                                        lane_bytes, lanes, recs, sum, st, no);
 }
 
-int eth_blocks_per_cu() {
-  int blocks = 0;
-  hipError_t e =
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_eth_run_episodes<SeedSource>, kBlock, 0);
-  if (e != hipSuccess || blocks <= 0) blocks = 2;
-  return blocks;
-}
+int eth_blocks_per_cu() { return ev_blocks_per_cu(k_eth_run_episodes<SeedSource>); }
 
 // ---------------------------------------------------------------- lockstep gym lanes
-// engine.ml reset/step with host actions (cpr_reset / cpr_step) and the on-device rollout,
-// one lane region of eth_lane_bytes per env; reward = Δ head.rewards[0] (engine.ml:223)
-struct EthSlot {
-  eth::EthLane L;
-  uint64_t ep;
-  double last_ra;
-  int32_t live;
-};
 
-// ethereum_ssz.ml:43-56 normalizers through ssz_tools.ml NormalizeObs.to_float; the unit
-// encodings use host-tabulated libm values (tabs = [2/pi atan(i) | 0.5 + atan(i - N)/pi],
-// i < N), the lanes' state decides the orphan fields with the three dry-run payloads
-__device__ inline void eth_write_obs(const eth::EthObs& o, int unit, const double* tabs,
-                                     int32_t tn, double* out) {
-  const int32_t v[10] = {o.public_height,  o.public_work,
-                         o.private_height, o.private_work,
-                         o.diff_height,    o.diff_work,
-                         o.public_orphans, o.private_orphans_inclusive,
-                         o.private_orphans_exclusive, o.event};
-  const double pi = 3.141592653589793;
-  for (int j = 0; j < 10; ++j) {
-    const int32_t x = v[j];
-    if (!unit || j == 9) {
-      out[j] = (double)x;
-    } else if (j == 4 || j == 5) {
-      out[j] = (x > -tn && x < tn) ? tabs[2 * tn + x] : 0.5 + (1.0 / pi * atan((double)x / 1.0));
-    } else {
-      out[j] = x < tn ? tabs[x] : 2.0 / pi * atan((double)x / 1.0);
-    }
-  }
-}
-
-__device__ inline void eth_slot_reset(const eth::EthParams& P, uint64_t seed, const eth::EthMem& M,
-                                      EthSlot& SL, uint64_t ep) {
-  SL.ep = ep;
-  SL.last_ra = 0.0;
-  SL.live = 1;
-  SL.L.gym_reset(P, make_stream(seed, ep), M);
-}
-
-__device__ inline eth::EthMem eth_lane_mem(const eth::EthParams& P, uint8_t* mem,
-                                           int64_t lane_bytes, int64_t i) {
-  return eth::eth_mem_at(mem + i * lane_bytes, P.cap_b, P.cap_e, P.n);
-}
-
-// LT: per-lane thresholds (lane_t); two instantiations, see k_reset in kernels.hip
 template <bool LT>
-__global__ __launch_bounds__(kBlock) void k_eth_reset(eth::EthParams P, uint64_t seed,
-                                                       uint8_t* mem, int64_t lane_bytes,
-                                                       EthSlot* slots, int64_t n,
-                                                       const uint8_t* mask, const uint64_t* eps,
-                                                       int unit, const double* tabs, int32_t tn,
-                                                       double* obs,
-                                                       const uint64_t* lane_t) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if constexpr (LT) P.t_att = lane_t[i];  // the lane's own alpha (cpr_lane_env_set)
-  const eth::EthMem M = eth_lane_mem(P, mem, lane_bytes, i);
-  EthSlot SL = slots[i];
-  if (mask == nullptr || mask[i]) eth_slot_reset(P, seed, M, SL, eps ? eps[i] : (uint64_t)i);
-  eth_write_obs(SL.L.observe(P, M, true), unit, tabs, tn, obs + 10 * i);
-  slots[i] = SL;
+__global__ __launch_bounds__(kBlock) void k_eth_reset(
+    eth::EthParams P, uint64_t seed, uint8_t* mem, int64_t lane_bytes, EthSlot* slots, int64_t n,
+    const uint8_t* mask, const uint64_t* eps, int unit, const double* tabs, int32_t tn, double* obs,
+    const uint64_t* lane_t) {
+  ev_reset_body<EthAdapter, LT>(P, seed, mem, lane_bytes, slots, n, mask, eps, unit, tabs, tn,
+                                obs, lane_t);
 }
 
-__device__ inline void eth_info(const eth::EthParams& P, const eth::EthMem& M, EthSlot& SL,
-                                int32_t hd, int64_t i, const StepBuffers& out) {
-  const eth::EBlock& h = SL.L.B(P, M, hd);
-  out.era[i] = (double)h.rew_att / 32.0;
-  out.erd[i] = (double)h.rew_def / 32.0;
-  out.eprog[i] = (double)h.work;
-  out.ect[i] = h.time;
-  out.est[i] = SL.L.now;
-  out.esteps[i] = SL.L.steps;
-  out.eacts[i] = SL.L.c_act;
-  out.hh[i] = h.height;
-  out.hm[i] = h.miner;
-}
-
-// LT: per-lane thresholds (lane_t); two instantiations, see k_reset in kernels.hip
 template <bool LT>
-__global__ __launch_bounds__(kBlock) void k_eth_step(eth::EthParams P, uint64_t seed,
-                                                      uint8_t* mem, int64_t lane_bytes,
-                                                      EthSlot* slots, int64_t n,
-                                                      const int32_t* actions, int unit,
-                                                      const double* tabs, int32_t tn,
-                                                      StepBuffers out,
-                                                      const uint64_t* lane_t) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if constexpr (LT) P.t_att = lane_t[i];  // the lane's own alpha (cpr_lane_env_set)
-  const eth::EthMem M = eth_lane_mem(P, mem, lane_bytes, i);
-  EthSlot SL = slots[i];
-  bool done = false;
-  const int32_t hd = SL.L.gym_step(P, make_stream(seed, SL.ep), M, actions[i], &done);
-  const double ra = (double)SL.L.B(P, M, hd).rew_att / 32.0;
-  out.reward[i] = ra - SL.last_ra;  // engine.ml:223
-  out.done[i] = done ? 1 : 0;
-  out.status[i] = SL.L.status;
-  if (out.era) eth_info(P, M, SL, hd, i, out);
-  SL.last_ra = ra;
-  eth_write_obs(SL.L.observe(P, M, true), unit, tabs, tn, out.obs + 10 * i);
-  slots[i] = SL;
+__global__ __launch_bounds__(kBlock) void k_eth_step(
+    eth::EthParams P, uint64_t seed, uint8_t* mem, int64_t lane_bytes, EthSlot* slots, int64_t n,
+    const int32_t* actions, int unit, const double* tabs, int32_t tn, StepBuffers out,
+    const uint64_t* lane_t) {
+  ev_step_body<EthAdapter, LT>(P, seed, mem, lane_bytes, slots, n, actions, unit, tabs, tn, out,
+                               lane_t);
 }
 
-// n_steps lockstep steps per lane with the batch policy on the device, VecEnv auto-reset
-// (episode id + n), as k_bk_rollout
-__global__ __launch_bounds__(kBlock) CPR_EV_OCC void k_eth_rollout(eth::EthParams P, uint64_t seed,
-                                                         uint8_t* mem, int64_t lane_bytes,
-                                                         EthSlot* slots, int64_t n,
-                                                         int64_t n_steps, int unit,
-                                                         const double* tabs, int32_t tn,
-                                                         double* obs, double* reward,
-                                                         uint8_t* done_out, cpr_summary* sum) {
-  __shared__ int32_t hist[CPR_HIST_BINS];
-  if (threadIdx.x < CPR_HIST_BINS) hist[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  Acc acc = {};
-  int64_t steps_all = 0, acts_all = 0;
-  if (i < n) {
-    const eth::EthMem M = eth_lane_mem(P, mem, lane_bytes, i);
-    EthSlot SL = slots[i];
-    if (!SL.live) {
-      eth_slot_reset(P, seed, M, SL, (uint64_t)i);
-      acts_all += SL.L.c_act;
-    }
-    for (int64_t t = 0; t < n_steps; ++t) {
-      const eth::EthObs o = SL.L.observe(P, M, false);
-      const int32_t c0 = SL.L.c_act;
-      bool done = false;
-      const int32_t hd =
-          SL.L.gym_step(P, make_stream(seed, SL.ep), M, eth::lane_action(P, o), &done);
-      acts_all += SL.L.c_act - c0;
-      ++steps_all;
-      const eth::EBlock& h = SL.L.B(P, M, hd);
-      const double ra = (double)h.rew_att / 32.0;
-      const int64_t k = t * n + i;
-      if (reward) reward[k] = ra - SL.last_ra;
-      if (done_out) done_out[k] = done ? 1 : 0;
-      SL.last_ra = ra;
-      if (done) {
-        const int32_t a = h.rew_att, d = h.rew_def;
-        const double rel = (a + d) != 0 ? (double)a / (double)(a + d) : 0.0;
-        acc_episode(acc, (int64_t)a << 15, (int64_t)d << 15, (int64_t)h.work << 20, rel,
-                    h.height, SL.L.steps, SL.L.c_act, SL.L.status, hist);
-        eth_slot_reset(P, seed, M, SL, SL.ep + (uint64_t)n);
-        acts_all += SL.L.c_act;
-      }
-      if (obs) eth_write_obs(SL.L.observe(P, M, true), unit, tabs, tn, obs + 10 * k);
-    }
-    slots[i] = SL;
-  }
-  acc.steps = steps_all;
-  acc.activations = acts_all;
-  __syncthreads();
-  block_flush(acc, hist, sum);
+__global__ __launch_bounds__(kBlock) CPR_EV_OCC void k_eth_rollout(
+    eth::EthParams P, uint64_t seed, uint8_t* mem, int64_t lane_bytes, EthSlot* slots, int64_t n,
+    int64_t n_steps, int unit, const double* tabs, int32_t tn, double* obs, double* reward,
+    uint8_t* done_out, cpr_summary* sum) {
+  ev_rollout_body<EthAdapter>(P, seed, mem, lane_bytes, slots, n, n_steps, unit, tabs, tn, obs,
+                              reward, done_out, sum, SlabView{nullptr, 0, 0, 0, 0},
+                              EthAdapter::kRollLpw);
 }
 
 __global__ void k_eth_observe_fields(eth::EthParams P, uint8_t* mem, int64_t lane_bytes,
                                      const EthSlot* slots, int64_t n, int32_t* f) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const eth::EthMem M = eth_lane_mem(P, mem, lane_bytes, i);
-  eth::EthLane L = slots[i].L;
-  const eth::EthObs o = L.observe(P, M, true);
-  int32_t* g = f + 10 * i;
-  g[0] = o.public_height;
-  g[1] = o.public_work;
-  g[2] = o.private_height;
-  g[3] = o.private_work;
-  g[4] = o.diff_height;
-  g[5] = o.diff_work;
-  g[6] = o.public_orphans;
-  g[7] = o.private_orphans_inclusive;
-  g[8] = o.private_orphans_exclusive;
-  g[9] = o.event;
+  ev_observe_fields_body<EthAdapter>(P, mem, lane_bytes, slots, n, f);
 }
 
 // engine.ml:258-261: decode (ssz_tools.ml NormalizeObs.of_float) and apply the policy
@@ -777,65 +627,46 @@ __global__ void k_eth_policy(int32_t policy, int unit, const double* obs, int64_
   actions[i] = eth::eth_policy_t(policy, o, table, dim);
 }
 
-static unsigned eth_grid_of(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 hipError_t launch_eth_reset(const eth::EthParams& P, uint64_t seed, uint8_t* mem,
                             int64_t lane_bytes, void* slots, int64_t n, const uint8_t* mask,
                             const uint64_t* eps, int unit, const double* tabs, int32_t tn,
                             double* obs, hipStream_t st, const uint64_t* lane_t) {
-  CPR_LAYOUT_GUARD(lane_bytes, eth::eth_lane_bytes(P.cap_b, P.cap_e, P.n));
-  if (lane_t)
-    hipLaunchKernelGGL(k_eth_reset<true>, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
-                       lane_bytes, (EthSlot*)slots, n, mask, eps, unit, tabs, tn, obs, lane_t);
-  else
-    hipLaunchKernelGGL(k_eth_reset<false>, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
-                       lane_bytes, (EthSlot*)slots, n, mask, eps, unit, tabs, tn, obs, lane_t);
-  return hipGetLastError();
+  return ev_launch_lanes<EthAdapter>(lane_t ? k_eth_reset<true> : k_eth_reset<false>, lane_bytes,
+                                     n, st, P, seed, mem, lane_bytes, (EthSlot*)slots, n, mask,
+                                     eps, unit, tabs, tn, obs, lane_t);
 }
 
 hipError_t launch_eth_step(const eth::EthParams& P, uint64_t seed, uint8_t* mem,
                            int64_t lane_bytes, void* slots, int64_t n, const int32_t* actions,
                            int unit, const double* tabs, int32_t tn, const StepBuffers& b,
                            hipStream_t st, const uint64_t* lane_t) {
-  CPR_LAYOUT_GUARD(lane_bytes, eth::eth_lane_bytes(P.cap_b, P.cap_e, P.n));
-  if (lane_t)
-    hipLaunchKernelGGL(k_eth_step<true>, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
-                       lane_bytes, (EthSlot*)slots, n, actions, unit, tabs, tn, b, lane_t);
-  else
-    hipLaunchKernelGGL(k_eth_step<false>, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
-                       lane_bytes, (EthSlot*)slots, n, actions, unit, tabs, tn, b, lane_t);
-  return hipGetLastError();
+  return ev_launch_lanes<EthAdapter>(lane_t ? k_eth_step<true> : k_eth_step<false>, lane_bytes, n,
+                                     st, P, seed, mem, lane_bytes, (EthSlot*)slots, n, actions,
+                                     unit, tabs, tn, b, lane_t);
 }
 
 hipError_t launch_eth_rollout(const eth::EthParams& P, uint64_t seed, uint8_t* mem,
                               int64_t lane_bytes, void* slots, int64_t n, int64_t n_steps,
                               int unit, const double* tabs, int32_t tn, double* obs,
                               double* reward, uint8_t* done, cpr_summary* sum, hipStream_t st) {
-  CPR_LAYOUT_GUARD(lane_bytes, eth::eth_lane_bytes(P.cap_b, P.cap_e, P.n));
-  hipLaunchKernelGGL(k_eth_rollout, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, seed, mem,
-                     lane_bytes, (EthSlot*)slots, n, n_steps, unit, tabs, tn, obs, reward, done,
-                     sum);
-  return hipGetLastError();
+  return ev_launch_rollout<EthAdapter>(k_eth_rollout, P, seed, mem, lane_bytes, slots, n,
+                                       n_steps, unit, tabs, tn, obs, reward, done, sum, st);
 }
 
 hipError_t launch_eth_observe_fields(const eth::EthParams& P, uint8_t* mem, int64_t lane_bytes,
                                      const void* slots, int64_t n, int32_t* f, hipStream_t st) {
-  CPR_LAYOUT_GUARD(lane_bytes, eth::eth_lane_bytes(P.cap_b, P.cap_e, P.n));
-  hipLaunchKernelGGL(k_eth_observe_fields, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, P, mem,
-                     lane_bytes, (const EthSlot*)slots, n, f);
-  return hipGetLastError();
+  return ev_launch_lanes<EthAdapter>(k_eth_observe_fields, lane_bytes, n, st, P, mem, lane_bytes,
+                                     (const EthSlot*)slots, n, f);
 }
 
 hipError_t launch_eth_cursor(const void* slots, int64_t n, const LaneCursor& c, hipStream_t st) {
-  hipLaunchKernelGGL(k_slot_cursor<EthSlot>, dim3(eth_grid_of(n)), dim3(kBlock), 0, st,
-                     (const EthSlot*)slots, n, c);
-  return hipGetLastError();
+  return ev_launch_cursor<EthAdapter>(slots, n, c, st);
 }
 
 hipError_t launch_eth_policy(int32_t policy, int unit, const double* obs, int64_t n,
                              const uint8_t* table, int32_t dim, int32_t* actions,
                              hipStream_t st) {
-  hipLaunchKernelGGL(k_eth_policy, dim3(eth_grid_of(n)), dim3(kBlock), 0, st, policy, unit, obs,
+  hipLaunchKernelGGL(k_eth_policy, dim3(grid_of(n)), dim3(kBlock), 0, st, policy, unit, obs,
                      n, table, dim, actions);
   return hipGetLastError();
 }

@@ -11,7 +11,9 @@
 // order, so every output is identical to the plain loop's (the parity tests compare both
 // to the oracle); only the wave's interleaving of lanes changes.
 //
-// The adapter A gives the protocol specifics: A::Lane, A::Par, A::Mem and
+// The adapter A (BkAdapter, EthAdapter, TsAdapter in the protocols' kernel units; its further
+// hooks for the kernel bodies are listed in ev_kernels.h) gives the protocol specifics:
+// A::Lane, A::Par, A::Mem and
 //   begin(L, P, S, M)            init (simulator.ml:233-332) for a fresh episode
 //   gym(P)                       engine.ml gym episode (else Simulator.loop ~activations)
 //   loop_attacker(P)             loop mode: node 0's OnNode runs the attack space
@@ -142,9 +144,10 @@ __device__ inline void ev_exec(typename A::Lane& L, const typename A::Par& P, co
   L.handle(P, S, M, c.ev, c.s);
 }
 
-// ---- rollouts (k_bk_rollout / k_ts_rollout: lockstep steps with the on-device policy,
-// VecEnv auto-reset) under the same dispatch. A lane starts a launch at the attacker's
-// decision point (prepared); its items are the events up to the next interaction
+// ---- rollouts (ev_kernels.h ev_rollout_body, the body of k_bk_rollout / k_ts_rollout:
+// lockstep steps with the on-device policy, VecEnv auto-reset) under the same dispatch. A
+// lane starts a launch at the attacker's decision point (prepared); its items are the events
+// up to the next interaction
 // (engine.ml:108-121 skip_to_interaction, with the PoW substitution), and the interaction
 // itself ends the step: head / done / reward, then the observation and the next action, or
 // on done the reset (init, whose events up to the first interaction run as items as well).

@@ -75,6 +75,20 @@ def test_ts_gym_records_match_oracle(ctx, alpha, gamma, policy, scheme, sel, k, 
     assert (rec["n_steps"][ok] == steps).all()
 
 
+@pytest.mark.parametrize("lpw", [None, "16"])
+def test_ts_gym_lanes_per_wave_ragged(ctx, monkeypatch, lpw):
+    # CPR_EV_LPW (event_lanes_per_wave): 16 of a wave's 64 lanes run episodes, the others
+    # idle. 300 episodes are no multiple of 16, so the last workgroup's last wave is ragged
+    if lpw is None:
+        monkeypatch.delenv("CPR_EV_LPW", raising=False)
+    else:
+        monkeypatch.setenv("CPR_EV_LPW", lpw)
+    cfg, keep = _cfg(alpha=0.33, gamma=0.5, policy=L.TS_POLICY_AVOID_LOSS, k=2, max_steps=64,
+                     seed=0x1A9E5)
+    s, rec, ok = _compare(cfg, keep, 300)
+    assert (rec["n_steps"][ok] == 64).all()
+
+
 @pytest.mark.parametrize("policy", [0, 1, 3, 6])
 def test_ts_two_agents_loop_matches_oracle(ctx, policy):
     # BASELINE configs[3]: two agents, k = 8, discount, heuristic

@@ -50,14 +50,16 @@ def main():
         for p in procs:
             assert p.wait() == 0
         objs = [str((vdir if s in EV else objdir) / (s + ".o"))
-                for s in ["kernels.hip", *EV, "kernels_fc16.hip", "kernels_generic.hip"]]
+                for s in ["kernels.hip", *EV, "ev_plan.hip", "kernels_fc16.hip",
+                          "kernels_generic.hip"]]
         subprocess.run([G._hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o",
                         str(out / f"{tag}{w}.so")], check=True)
         print("built", out / f"{tag}{w}.so")
 
 
-ALL = ["kernels.hip", "kernels_nak_fused.hip", "kernels_nak_rollout.hip", *EV, "kernels_fc16.hip",
-       "kernels_generic.hip", "kernels_policy.hip", "kernels_ppo.hip", "kernels_dqn.hip"]
+ALL = ["kernels.hip", "kernels_nak_fused.hip", "kernels_nak_rollout.hip", *EV, "ev_plan.hip",
+       "kernels_fc16.hip", "kernels_generic.hip", "kernels_policy.hip", "kernels_ppo.hip",
+       "kernels_dqn.hip"]
 
 
 def build_def(objdir, out, flags, tag, tus, defs):

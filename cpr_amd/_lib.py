@@ -524,6 +524,49 @@ class MdpViResultC(ctypes.Structure):
     ]
 
 
+MDP_PE_REACHABLE, MDP_PE_ALL = 0, 1  # enum cpr_mdp_pe_states
+MDP_PE_CONVERGED, MDP_PE_MAX_ITER, MDP_PE_NOT_CONVERGED = 0, 1, 2  # enum cpr_mdp_pe_status
+
+
+class MdpPeC(ctypes.Structure):
+    """cpr_mdp_pe: E evaluations (point, policy, start states) over one cpr_mdp."""
+
+    _fields_ = [
+        ("E", ctypes.c_int64),
+        ("point", ctypes.c_void_p),
+        ("policy", ctypes.c_void_p),
+        ("states", ctypes.c_int32),
+        ("n_start", ctypes.c_int32),
+        ("start_state", ctypes.c_void_p),
+        ("start_prob", ctypes.c_void_p),
+    ]
+
+
+class MdpPeOptsC(ctypes.Structure):
+    """cpr_mdp_pe_opts."""
+
+    _fields_ = [
+        ("theta", ctypes.c_double),
+        ("discount", ctypes.c_double),
+        ("max_iter", ctypes.c_int64),
+        ("path", ctypes.c_int32),
+    ]
+
+
+class MdpPeResultC(ctypes.Structure):
+    """cpr_mdp_pe_result: the caller's arrays and the two scalars the call fills in."""
+
+    _fields_ = [
+        ("reward", ctypes.c_void_p),
+        ("progress", ctypes.c_void_p),
+        ("iter", ctypes.c_void_p),
+        ("delta", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+        ("path_used", ctypes.c_int32),
+        ("kernel_ms", ctypes.c_double),
+    ]
+
+
 class CTrace(ctypes.Structure):
     _fields_ = [
         ("n_episodes", ctypes.c_int64),
@@ -673,6 +716,8 @@ EXPORTS = [
     "cpr_stream_fill",
     "cpr_mdp_vi_opts_default",
     "cpr_mdp_value_iteration",
+    "cpr_mdp_pe_opts_default",
+    "cpr_mdp_policy_evaluation",
 ]
 
 
@@ -757,6 +802,9 @@ def _declare(L):
     ]
     L.cpr_mdp_vi_opts_default.argtypes = [P(MdpViOptsC)]
     L.cpr_mdp_value_iteration.argtypes = [vp, P(MdpC), P(MdpViOptsC), P(MdpViResultC)]
+    L.cpr_mdp_pe_opts_default.argtypes = [P(MdpPeOptsC)]
+    L.cpr_mdp_policy_evaluation.argtypes = [vp, P(MdpC), P(MdpPeC), P(MdpPeOptsC),
+                                            P(MdpPeResultC)]
 
 
 def lib():

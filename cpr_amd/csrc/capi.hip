@@ -4654,26 +4654,14 @@ static int64_t mdp_sweep_cap() {
   return kMdpSweepCap;
 }
 
-int cpr_mdp_value_iteration(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_vi_opts* opts,
-                            cpr_mdp_vi_result* res) {
-  if (!ctx || !mdp || !opts || !res) return fail(CPR_E_INVALID_ARG, "NULL argument");
-  CPR_ENTER(ctx);
-  // everything is checked before the first allocation or launch; a used slot is checked whether
-  // or not its action is valid (the host solver would read value[dst] of such a slot too)
+// The checks of a cpr_mdp that both MDP entries make before anything is allocated or launched;
+// a used slot is checked whether or not its action is valid (the host solver would read
+// value[dst] of such a slot too)
+static int mdp_check(const cpr_mdp* mdp) {
   if (mdp->S < 1 || mdp->A < 1 || mdp->T < 1 || mdp->P < 1)
     return fail(CPR_E_INVALID_ARG, "mdp: S, A, T and P must be at least 1");
   if (!mdp->dst || !mdp->used || !mdp->valid || !mdp->rew || !mdp->prg || !mdp->prb)
     return fail(CPR_E_INVALID_ARG, "mdp: NULL array");
-  if (!res->value || !res->progress || !res->policy || !res->iter || !res->delta || !res->status)
-    return fail(CPR_E_INVALID_ARG, "result: NULL array");
-  if (!(opts->discount > 0.0 && opts->discount <= 1.0))
-    return fail(CPR_E_INVALID_ARG, "discount must be in (0, 1]");
-  if (!(opts->stop_delta >= 0.0)) return fail(CPR_E_INVALID_ARG, "stop_delta must be >= 0");
-  if (opts->max_iter < 0) return fail(CPR_E_INVALID_ARG, "max_iter must be >= 0");
-  if (opts->stop_delta == 0.0 && opts->max_iter == 0)
-    return fail(CPR_E_INVALID_ARG, "infinite iteration: stop_delta == 0 and max_iter == 0");
-  if (opts->path < CPR_MDP_VI_AUTO || opts->path > CPR_MDP_VI_GLOBAL)
-    return fail(CPR_E_INVALID_ARG, "path: expected 0 (auto), 1 (resident) or 2 (global)");
   const int64_t S = mdp->S, A = mdp->A, T = mdp->T, P = mdp->P;
   const int64_t AT = A * T;  // < 2^62
   if (AT > ((int64_t)1 << 36) / S || AT * S > ((int64_t)1 << 36) / P)
@@ -4689,6 +4677,129 @@ int cpr_mdp_value_iteration(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_vi_o
       if (!std::isfinite(mdp->prb[p * slots + i]))
         return fail(CPR_E_INVALID_ARG, "mdp: a used slot's prb is not finite");
   }
+  return CPR_OK;
+}
+
+// A checked cpr_mdp on the device in the kernels' layout: state index fastest, unused slots
+// marked by dst = -1. The host copies live as long as the device ones.
+struct MdpUpload {
+  std::vector<int32_t> dst_t;
+  std::vector<uint8_t> valid_t;
+  std::vector<double> rew_t, prg_t, prb_t;
+  DevBuf d_dst, d_valid, d_rew, d_prg, d_prb;
+  MdpDev M{};
+};
+
+static int mdp_upload(const cpr_mdp* mdp, MdpUpload& u, hipStream_t st) {
+  const int64_t S = mdp->S, A = mdp->A, T = mdp->T, P = mdp->P;
+  const int64_t AT = A * T, slots = AT * S;
+  try {  // no exception may cross the C boundary
+    u.dst_t.resize((size_t)slots);
+    u.valid_t.resize((size_t)(A * S));
+    u.rew_t.resize((size_t)slots);
+    u.prg_t.resize((size_t)slots);
+    u.prb_t.resize((size_t)(slots * P));
+  } catch (const std::exception&) {
+    return fail(CPR_E_CAPACITY, "mdp: out of host memory for the upload copies");
+  }
+  for (int64_t s = 0; s < S; ++s) {
+    for (int64_t a = 0; a < A; ++a) u.valid_t[a * S + s] = mdp->valid[s * A + a] ? 1 : 0;
+    for (int64_t j = 0; j < AT; ++j) {
+      const int64_t from = s * AT + j, to = j * S + s;
+      const bool use = mdp->used[from] != 0;  // the kernels load unused slots too: dst -1, zeros
+      u.dst_t[to] = use ? mdp->dst[from] : -1;
+      u.rew_t[to] = use ? mdp->rew[from] : 0.0;
+      u.prg_t[to] = use ? mdp->prg[from] : 0.0;
+      for (int64_t p = 0; p < P; ++p)
+        u.prb_t[p * slots + to] = use ? mdp->prb[p * slots + from] : 0.0;
+    }
+  }
+  HIP_TRY(u.d_dst.ensure((size_t)slots * 4));
+  HIP_TRY(u.d_valid.ensure((size_t)(A * S)));
+  HIP_TRY(u.d_rew.ensure((size_t)slots * 8));
+  HIP_TRY(u.d_prg.ensure((size_t)slots * 8));
+  HIP_TRY(u.d_prb.ensure((size_t)(slots * P) * 8));
+  HIP_TRY(hipMemcpyAsync(u.d_dst.p, u.dst_t.data(), (size_t)slots * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(u.d_valid.p, u.valid_t.data(), (size_t)(A * S), hipMemcpyHostToDevice,
+                         st));
+  HIP_TRY(hipMemcpyAsync(u.d_rew.p, u.rew_t.data(), (size_t)slots * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(u.d_prg.p, u.prg_t.data(), (size_t)slots * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(u.d_prb.p, u.prb_t.data(), (size_t)(slots * P) * 8,
+                         hipMemcpyHostToDevice, st));
+  u.M = MdpDev{(int32_t)S, (int32_t)A, (int32_t)T, (int32_t)P, (const int32_t*)u.d_dst.p,
+               (const uint8_t*)u.d_valid.p, (const double*)u.d_rew.p, (const double*)u.d_prg.p,
+               (const double*)u.d_prb.p};
+  return CPR_OK;
+}
+
+struct MdpEvents {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~MdpEvents() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
+// The sweeps of either entry, between two events: every solve stops after `limit` sweeps at the
+// latest, so both loops end: the resident one after limit / kMdpSweepsPerLaunch + 1 launches,
+// the global one after launch limit + 1 (which records the stop of sweep `limit`). `status` is
+// the host copy of the device's `d_status`, read between launches; `done`: none is running.
+// (a template, so that each entry's launches are called directly: C++ linkage inside this block)
+extern "C++" template <class LaunchResident, class LaunchSweep>
+static int mdp_drive(bool resident, int64_t limit, std::vector<int32_t>& status,
+                     const void* d_status, hipStream_t st, MdpEvents& ev,
+                     const LaunchResident& launch_resident, const LaunchSweep& launch_sweep,
+                     bool& done) {
+  auto all_stopped = [&]() {
+    for (int32_t v : status)
+      if (v == kMdpRunning) return false;
+    return true;
+  };
+  HIP_TRY(hipEventCreate(&ev.e0));
+  HIP_TRY(hipEventCreate(&ev.e1));
+  HIP_TRY(hipEventRecord(ev.e0, st));
+  done = false;
+  if (resident) {
+    const int64_t launches = limit / kMdpSweepsPerLaunch + 1;
+    for (int64_t l = 0; l < launches && !done; ++l) {
+      HIP_TRY(launch_resident());
+      HIP_TRY(hipMemcpyAsync(status.data(), d_status, status.size() * 4, hipMemcpyDeviceToHost,
+                             st));
+      HIP_TRY(hipStreamSynchronize(st));
+      done = all_stopped();
+    }
+  } else {
+    for (int64_t k = 1; k <= limit + 1 && !done;) {
+      for (int n = 0; n < kMdpReadbackEvery && k <= limit + 1; ++n, ++k)
+        HIP_TRY(launch_sweep(k));
+      HIP_TRY(hipMemcpyAsync(status.data(), d_status, status.size() * 4, hipMemcpyDeviceToHost,
+                             st));
+      HIP_TRY(hipStreamSynchronize(st));
+      done = all_stopped();
+    }
+  }
+  HIP_TRY(hipEventRecord(ev.e1, st));
+  return CPR_OK;
+}
+
+int cpr_mdp_value_iteration(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_vi_opts* opts,
+                            cpr_mdp_vi_result* res) {
+  if (!ctx || !mdp || !opts || !res) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  CPR_ENTER(ctx);
+  // everything is checked before the first allocation or launch
+  if (const int rc = mdp_check(mdp)) return rc;
+  if (!res->value || !res->progress || !res->policy || !res->iter || !res->delta || !res->status)
+    return fail(CPR_E_INVALID_ARG, "result: NULL array");
+  if (!(opts->discount > 0.0 && opts->discount <= 1.0))
+    return fail(CPR_E_INVALID_ARG, "discount must be in (0, 1]");
+  if (!(opts->stop_delta >= 0.0)) return fail(CPR_E_INVALID_ARG, "stop_delta must be >= 0");
+  if (opts->max_iter < 0) return fail(CPR_E_INVALID_ARG, "max_iter must be >= 0");
+  if (opts->stop_delta == 0.0 && opts->max_iter == 0)
+    return fail(CPR_E_INVALID_ARG, "infinite iteration: stop_delta == 0 and max_iter == 0");
+  if (opts->path < CPR_MDP_VI_AUTO || opts->path > CPR_MDP_VI_GLOBAL)
+    return fail(CPR_E_INVALID_ARG, "path: expected 0 (auto), 1 (resident) or 2 (global)");
+  const int64_t S = mdp->S, A = mdp->A, T = mdp->T, P = mdp->P;
+  const int64_t AT = A * T;
   HIP_TRY(hipSetDevice(ctx->device));
   const bool fits = mdp_resident_fits(S);
   if (opts->path == CPR_MDP_VI_RESIDENT && !fits)
@@ -4700,39 +4811,17 @@ int cpr_mdp_value_iteration(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_vi_o
   if (!resident && chunks * P > INT32_MAX)
     return fail(CPR_E_CAPACITY, "path global: more than 2^31 workgroups per sweep");
 
-  // the kernels' layout: state index fastest, unused slots marked by dst = -1
-  std::vector<int32_t> dst_t, status;
-  std::vector<uint8_t> valid_t;
-  std::vector<double> rew_t, prg_t, prb_t;
-  try {  // no exception may cross the C boundary
-    dst_t.resize((size_t)slots);
+  std::vector<int32_t> status;
+  try {
     status.resize((size_t)P);
-    valid_t.resize((size_t)(A * S));
-    rew_t.resize((size_t)slots);
-    prg_t.resize((size_t)slots);
-    prb_t.resize((size_t)(slots * P));
   } catch (const std::exception&) {
     return fail(CPR_E_CAPACITY, "mdp: out of host memory for the upload copies");
   }
-  for (int64_t s = 0; s < S; ++s) {
-    for (int64_t a = 0; a < A; ++a) valid_t[a * S + s] = mdp->valid[s * A + a] ? 1 : 0;
-    for (int64_t j = 0; j < AT; ++j) {
-      const int64_t from = s * AT + j, to = j * S + s;
-      const bool u = mdp->used[from] != 0;  // the kernels load unused slots too: dst -1, zeros
-      dst_t[to] = u ? mdp->dst[from] : -1;
-      rew_t[to] = u ? mdp->rew[from] : 0.0;
-      prg_t[to] = u ? mdp->prg[from] : 0.0;
-      for (int64_t p = 0; p < P; ++p) prb_t[p * slots + to] = u ? mdp->prb[p * slots + from] : 0.0;
-    }
-  }
-  DevBuf d_dst, d_valid, d_rew, d_prg, d_prb, d_val[2], d_pro[2], d_pol, d_status, d_iter, d_delta,
-      d_acc;
+  hipStream_t st = ctx->stream;
+  MdpUpload up;
+  if (const int rc = mdp_upload(mdp, up, st)) return rc;
+  DevBuf d_val[2], d_pro[2], d_pol, d_status, d_iter, d_delta, d_acc;
   const size_t vec = (size_t)(P * S) * 8;
-  HIP_TRY(d_dst.ensure((size_t)slots * 4));
-  HIP_TRY(d_valid.ensure((size_t)(A * S)));
-  HIP_TRY(d_rew.ensure((size_t)slots * 8));
-  HIP_TRY(d_prg.ensure((size_t)slots * 8));
-  HIP_TRY(d_prb.ensure((size_t)(slots * P) * 8));
   for (int i = 0; i < (resident ? 1 : 2); ++i) {
     HIP_TRY(d_val[i].ensure(vec));
     HIP_TRY(d_pro[i].ensure(vec));
@@ -4744,21 +4833,12 @@ int cpr_mdp_value_iteration(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_vi_o
   HIP_TRY(d_iter.ensure((size_t)P * 8));
   HIP_TRY(d_delta.ensure((size_t)P * 8));
   HIP_TRY(d_acc.ensure((size_t)P * 24));
-  hipStream_t st = ctx->stream;
-  HIP_TRY(hipMemcpyAsync(d_dst.p, dst_t.data(), (size_t)slots * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_valid.p, valid_t.data(), (size_t)(A * S), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_rew.p, rew_t.data(), (size_t)slots * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_prg.p, prg_t.data(), (size_t)slots * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_prb.p, prb_t.data(), (size_t)(slots * P) * 8, hipMemcpyHostToDevice,
-                         st));
   HIP_TRY(hipMemsetAsync(d_status.p, 0xFF, (size_t)P * 4, st));  // kMdpRunning
   HIP_TRY(hipMemsetAsync(d_iter.p, 0, (size_t)P * 8, st));
   HIP_TRY(hipMemsetAsync(d_delta.p, 0, (size_t)P * 8, st));
   HIP_TRY(hipMemsetAsync(d_acc.p, 0, (size_t)P * 24, st));
 
-  MdpDev M{(int32_t)S, (int32_t)A, (int32_t)T, (int32_t)P, (const int32_t*)d_dst.p,
-           (const uint8_t*)d_valid.p, (const double*)d_rew.p, (const double*)d_prg.p,
-           (const double*)d_prb.p};
+  const MdpDev& M = up.M;
   MdpRun R{};
   R.stop_delta = opts->stop_delta;
   R.discount = opts->discount;
@@ -4774,44 +4854,14 @@ int cpr_mdp_value_iteration(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_vi_o
   R.delta = (double*)d_delta.p;
   R.acc = (unsigned long long*)d_acc.p;
 
-  // every point stops after `limit` sweeps at the latest, so both loops below end: the resident
-  // one after limit / kMdpSweepsPerLaunch + 1 launches, the global one after launch limit + 1
-  // (which records the stop of sweep `limit`)
   const int64_t limit = opts->max_iter > 0 ? opts->max_iter : R.cap;
-  auto all_stopped = [&]() {
-    for (int32_t v : status)
-      if (v == kMdpRunning) return false;
-    return true;
-  };
-  struct Events {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Events() {
-      if (e0) (void)hipEventDestroy(e0);
-      if (e1) (void)hipEventDestroy(e1);
-    }
-  } ev;
-  HIP_TRY(hipEventCreate(&ev.e0));
-  HIP_TRY(hipEventCreate(&ev.e1));
-  HIP_TRY(hipEventRecord(ev.e0, st));
+  MdpEvents ev;
   bool done = false;
-  if (resident) {
-    const int64_t launches = limit / kMdpSweepsPerLaunch + 1;
-    for (int64_t l = 0; l < launches && !done; ++l) {
-      HIP_TRY(launch_mdp_resident(M, R, st));
-      HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      done = all_stopped();
-    }
-  } else {
-    for (int64_t k = 1; k <= limit + 1 && !done;) {
-      for (int n = 0; n < kMdpReadbackEvery && k <= limit + 1; ++n, ++k)
-        HIP_TRY(launch_mdp_sweep(M, R, k, st));
-      HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      done = all_stopped();
-    }
-  }
-  HIP_TRY(hipEventRecord(ev.e1, st));
+  if (const int rc = mdp_drive(
+          resident, limit, status, d_status.p, st, ev,
+          [&]() { return launch_mdp_resident(M, R, st); },
+          [&](int64_t k) { return launch_mdp_sweep(M, R, k, st); }, done))
+    return rc;
   if (!done) return fail(CPR_E_INTERNAL, "mdp value iteration: a point outlived its sweep limit");
 
   HIP_TRY(hipMemcpyAsync(res->iter, d_iter.p, (size_t)P * 8, hipMemcpyDeviceToHost, st));
@@ -4834,6 +4884,220 @@ int cpr_mdp_value_iteration(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_vi_o
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   for (int64_t p = 0; p < P; ++p) res->status[p] = status[(size_t)p];
+  res->path_used = resident ? CPR_MDP_VI_RESIDENT : CPR_MDP_VI_GLOBAL;
+  res->kernel_ms = ms;
+  return CPR_OK;
+}
+
+int cpr_mdp_pe_opts_default(cpr_mdp_pe_opts* opts) {
+  if (!opts) return fail(CPR_E_INVALID_ARG, "opts is NULL");
+  opts->theta = 1e-6;
+  opts->discount = 1.0;
+  opts->max_iter = 0;
+  opts->path = CPR_MDP_VI_AUTO;
+  return CPR_OK;
+}
+
+// as mdp_sweep_cap, for policy evaluation: CPR_MDP_PE_SWEEP_CAP lowers it
+static int64_t mdp_pe_sweep_cap() {
+  if (const char* e = getenv("CPR_MDP_PE_SWEEP_CAP")) {
+    const long long v = atoll(e);
+    if (v >= 1 && v < kMdpSweepCap) return v;
+  }
+  return kMdpSweepCap;
+}
+
+// explicit_mdp.py:179-208 for every evaluation, folded into the policy: act[e][s] = policy[e][s]
+// where state s is included and has a policy entry, else -1 (the state stays 0)
+static void mdp_pe_included(const cpr_mdp* mdp, const cpr_mdp_pe* job, std::vector<int32_t>& act,
+                            std::vector<int32_t>& todo, std::vector<uint8_t>& seen) {
+  const int64_t S = mdp->S, A = mdp->A, T = mdp->T, slots = A * T * S;
+  for (int64_t e = 0; e < job->E; ++e) {
+    const int32_t* pol = job->policy + e * S;
+    int32_t* out = act.data() + e * S;
+    if (job->states == CPR_MDP_PE_ALL) {
+      for (int64_t s = 0; s < S; ++s) out[s] = pol[s] < 0 ? -1 : pol[s];
+      continue;
+    }
+    const double* prb = mdp->prb + (int64_t)job->point[e] * slots;
+    std::fill(seen.begin(), seen.end(), (uint8_t)0);
+    todo.clear();
+    for (int32_t i = 0; i < job->n_start; ++i) {
+      const int32_t s = job->start_state[e * job->n_start + i];
+      if (job->start_prob[e * job->n_start + i] > 0.0 && !seen[s]) {
+        seen[s] = 1;
+        todo.push_back(s);
+      }
+    }
+    while (!todo.empty()) {
+      const int32_t s = todo.back();
+      todo.pop_back();
+      if (pol[s] < 0) continue;  // a leaf
+      const int64_t base = ((int64_t)s * A + pol[s]) * T;
+      for (int64_t t = 0; t < T; ++t) {
+        if (!mdp->used[base + t] || prb[base + t] == 0.0) continue;
+        const int32_t d = mdp->dst[base + t];
+        if (!seen[d]) {
+          seen[d] = 1;
+          todo.push_back(d);
+        }
+      }
+    }
+    for (int64_t s = 0; s < S; ++s) out[s] = seen[s] && pol[s] >= 0 ? pol[s] : -1;
+  }
+}
+
+int cpr_mdp_policy_evaluation(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_pe* job,
+                              const cpr_mdp_pe_opts* opts, cpr_mdp_pe_result* res) {
+  if (!mdp || !job || !opts || !res) return fail(CPR_E_INVALID_ARG, "NULL argument");
+  // everything is checked before the context is touched, an allocation made or a launch issued
+  if (const int rc = mdp_check(mdp)) return rc;
+  if (!res->reward || !res->progress || !res->iter || !res->delta || !res->status)
+    return fail(CPR_E_INVALID_ARG, "result: NULL array");
+  if (!(opts->discount > 0.0 && opts->discount <= 1.0))
+    return fail(CPR_E_INVALID_ARG, "discount must be in (0, 1]");
+  if (!(opts->theta >= 0.0)) return fail(CPR_E_INVALID_ARG, "theta must be >= 0");
+  if (opts->max_iter < 0) return fail(CPR_E_INVALID_ARG, "max_iter must be >= 0");
+  if (opts->theta == 0.0 && opts->max_iter == 0)
+    return fail(CPR_E_INVALID_ARG, "infinite iteration: theta == 0 and max_iter == 0");
+  if (opts->path < CPR_MDP_VI_AUTO || opts->path > CPR_MDP_VI_GLOBAL)
+    return fail(CPR_E_INVALID_ARG, "path: expected 0 (auto), 1 (resident) or 2 (global)");
+  const int64_t S = mdp->S, A = mdp->A, T = mdp->T, P = mdp->P, E = job->E;
+  if (E < 1) return fail(CPR_E_INVALID_ARG, "job: E must be at least 1");
+  if (E > ((int64_t)1 << 36) / S)
+    return fail(CPR_E_INVALID_ARG, "job: more than 2^36 states over all evaluations");
+  if (!job->point || !job->policy) return fail(CPR_E_INVALID_ARG, "job: NULL array");
+  if (job->states != CPR_MDP_PE_REACHABLE && job->states != CPR_MDP_PE_ALL)
+    return fail(CPR_E_INVALID_ARG, "job: states: expected 0 (reachable) or 1 (all)");
+  for (int64_t e = 0; e < E; ++e)
+    if (job->point[e] < 0 || job->point[e] >= P)
+      return fail(CPR_E_INVALID_ARG, "job: a point is outside [0, P)");
+  for (int64_t i = 0; i < E * S; ++i) {
+    const int32_t a = job->policy[i];
+    if (a >= A || (a >= 0 && !mdp->valid[(i % S) * A + a]))
+      return fail(CPR_E_INVALID_ARG, "job: a policy entry names an action its state does not offer");
+  }
+  if (job->states == CPR_MDP_PE_REACHABLE) {
+    if (job->n_start < 1) return fail(CPR_E_INVALID_ARG, "job: n_start must be at least 1");
+    if (!job->start_state || !job->start_prob)
+      return fail(CPR_E_INVALID_ARG, "job: NULL start array");
+    if (E > ((int64_t)1 << 36) / job->n_start)
+      return fail(CPR_E_INVALID_ARG, "job: more than 2^36 start entries over all evaluations");
+    for (int64_t i = 0; i < E * job->n_start; ++i)
+      if (job->start_state[i] < 0 || job->start_state[i] >= S)
+        return fail(CPR_E_INVALID_ARG, "job: a start state is outside [0, S)");
+  }
+  if (!ctx) return fail(CPR_E_INVALID_ARG, "ctx is NULL");
+  CPR_ENTER(ctx);
+  HIP_TRY(hipSetDevice(ctx->device));
+  const bool fits = mdp_pe_resident_fits(S);
+  if (opts->path == CPR_MDP_VI_RESIDENT && !fits)
+    return fail(CPR_E_CAPACITY, "path resident: the states do not fit one workgroup's LDS");
+  const char* reread_env = getenv("CPR_MDP_PE_REREAD");  // measurements: never keep the slots
+  const bool reread = reread_env && atoi(reread_env) != 0;
+  const bool keep = !reread && mdp_pe_resident_keeps(S, (int32_t)T);
+  const bool resident =
+      opts->path == CPR_MDP_VI_RESIDENT ||
+      (opts->path == CPR_MDP_VI_AUTO && fits && mdp_pe_auto_resident(T * S, E, ctx->cus, keep));
+  const int64_t chunks = (S + kMdpBlock - 1) / kMdpBlock;
+  if (E > INT32_MAX || (!resident && chunks * E > INT32_MAX))
+    return fail(CPR_E_CAPACITY, "more than 2^31 workgroups per sweep");
+
+  std::vector<int32_t> status, act, todo;
+  std::vector<uint8_t> seen;
+  try {
+    status.resize((size_t)E);
+    act.resize((size_t)(E * S));
+    todo.reserve((size_t)S);
+    seen.resize((size_t)S);
+  } catch (const std::exception&) {
+    return fail(CPR_E_CAPACITY, "mdp: out of host memory for the upload copies");
+  }
+  mdp_pe_included(mdp, job, act, todo, seen);
+
+  hipStream_t st = ctx->stream;
+  MdpUpload up;
+  if (const int rc = mdp_upload(mdp, up, st)) return rc;
+  DevBuf d_rew[2], d_pro[2], d_act, d_point, d_status, d_iter, d_delta, d_acc;
+  const size_t vec = (size_t)(E * S) * 8;
+  for (int i = 0; i < (resident ? 1 : 2); ++i) {
+    HIP_TRY(d_rew[i].ensure(vec));
+    HIP_TRY(d_pro[i].ensure(vec));
+    HIP_TRY(hipMemsetAsync(d_rew[i].p, 0, vec, st));
+    HIP_TRY(hipMemsetAsync(d_pro[i].p, 0, vec, st));
+  }
+  HIP_TRY(d_act.ensure((size_t)(E * S) * 4));
+  HIP_TRY(d_point.ensure((size_t)E * 4));
+  HIP_TRY(d_status.ensure((size_t)E * 4));
+  HIP_TRY(d_iter.ensure((size_t)E * 8));
+  HIP_TRY(d_delta.ensure((size_t)E * 8));
+  HIP_TRY(d_acc.ensure((size_t)E * 24));
+  HIP_TRY(hipMemcpyAsync(d_act.p, act.data(), (size_t)(E * S) * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_point.p, job->point, (size_t)E * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(d_status.p, 0xFF, (size_t)E * 4, st));  // kMdpRunning
+  HIP_TRY(hipMemsetAsync(d_iter.p, 0, (size_t)E * 8, st));
+  HIP_TRY(hipMemsetAsync(d_delta.p, 0, (size_t)E * 8, st));
+  HIP_TRY(hipMemsetAsync(d_acc.p, 0, (size_t)E * 24, st));
+
+  const MdpDev& M = up.M;
+  MdpPeRun R{};
+  R.theta = opts->theta;
+  R.discount = opts->discount;
+  R.max_iter = opts->max_iter;
+  R.cap = mdp_pe_sweep_cap();
+  R.E = (int32_t)E;
+  R.reread = reread ? 1 : 0;
+  R.point = (const int32_t*)d_point.p;
+  R.act = (const int32_t*)d_act.p;
+  for (int i = 0; i < 2; ++i) {
+    R.reward[i] = (double*)d_rew[i].p;
+    R.progress[i] = (double*)d_pro[i].p;
+  }
+  R.status = (int32_t*)d_status.p;
+  R.iter = (int64_t*)d_iter.p;
+  R.delta = (double*)d_delta.p;
+  R.acc = (unsigned long long*)d_acc.p;
+
+  const int64_t limit = opts->max_iter > 0 ? opts->max_iter : R.cap;
+  MdpEvents ev;
+  bool done = false;
+  if (const int rc = mdp_drive(
+          resident, limit, status, d_status.p, st, ev,
+          [&]() { return launch_mdp_pe_resident(M, R, st); },
+          [&](int64_t k) { return launch_mdp_pe_sweep(M, R, k, st); }, done))
+    return rc;
+  if (!done)
+    return fail(CPR_E_INTERNAL, "mdp policy evaluation: an evaluation outlived its sweep limit");
+
+  HIP_TRY(hipMemcpyAsync(res->iter, d_iter.p, (size_t)E * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(res->delta, d_delta.p, (size_t)E * 8, hipMemcpyDeviceToHost, st));
+  if (resident) {
+    HIP_TRY(hipMemcpyAsync(res->reward, d_rew[0].p, vec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(res->progress, d_pro[0].p, vec, hipMemcpyDeviceToHost, st));
+  } else {
+    // the global path left an evaluation's vectors in the buffer its last sweep wrote: both
+    // buffers come down whole and each evaluation's rows are taken from its own
+    std::vector<double> other;
+    try {
+      other.resize((size_t)(E * S) * 2);
+    } catch (const std::exception&) {
+      return fail(CPR_E_CAPACITY, "mdp: out of host memory for the result copies");
+    }
+    HIP_TRY(hipMemcpyAsync(res->reward, d_rew[0].p, vec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(res->progress, d_pro[0].p, vec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(other.data(), d_rew[1].p, vec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(other.data() + E * S, d_pro[1].p, vec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t e = 0; e < E; ++e) {
+      if (!(res->iter[e] & 1)) continue;
+      std::copy_n(other.data() + e * S, S, res->reward + e * S);
+      std::copy_n(other.data() + E * S + e * S, S, res->progress + e * S);
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  for (int64_t e = 0; e < E; ++e) res->status[e] = status[(size_t)e];
   res->path_used = resident ? CPR_MDP_VI_RESIDENT : CPR_MDP_VI_GLOBAL;
   res->kernel_ms = ms;
   return CPR_OK;

@@ -77,6 +77,26 @@ class Context:
         [P][S][A][T] (or [S][A][T] for one point). Returns a dict of value, progress, policy
         [P][S], iter, delta, status [P], path_used ("resident" / "global") and kernel_ms.
         Invalid input raises ``CprError`` before anything is launched."""
+        m, keep = self._mdp_c(dst, used, valid, rew, prg, prb)
+        S, P = m.S, m.P
+        if path not in self.MDP_VI_PATHS:
+            raise ValueError(f"path: expected one of {sorted(self.MDP_VI_PATHS)}")
+        o = L.MdpViOptsC(float(stop_delta), float(discount), int(max_iter),
+                         self.MDP_VI_PATHS[path])
+        out = dict(value=np.zeros((P, S)), progress=np.zeros((P, S)),
+                   policy=np.zeros((P, S), np.int32), iter=np.zeros(P, np.int64),
+                   delta=np.zeros(P), status=np.zeros(P, np.int32))
+        r = L.MdpViResultC(*(out[k].ctypes.data for k in
+                             ("value", "progress", "policy", "iter", "delta", "status")))
+        L.check(L.lib().cpr_mdp_value_iteration(self.handle, ctypes.byref(m), ctypes.byref(o),
+                                                ctypes.byref(r)))
+        out["path_used"] = "resident" if r.path_used == L.MDP_VI_RESIDENT else "global"
+        out["kernel_ms"] = r.kernel_ms
+        return out
+
+    @staticmethod
+    def _mdp_c(dst, used, valid, rew, prg, prb):
+        """The cpr_mdp of the dense padded arrays and the arrays it points into."""
         dst = np.asarray(dst)
         if dst.dtype.kind not in "iu":
             raise ValueError("dst: expected an integer array")
@@ -98,20 +118,65 @@ class Context:
         if used.shape != dst.shape or rew.shape != dst.shape or prg.shape != dst.shape \
                 or valid.shape != (S, A) or prb.ndim != 4 or prb.shape[1:] != dst.shape:
             raise ValueError("the arrays' shapes do not agree with dst [S][A][T]")
-        P = prb.shape[0]
+        keep = (dst, used, valid, rew, prg, prb)
+        return L.MdpC(S, A, T, prb.shape[0], *(x.ctypes.data for x in keep)), keep
+
+    MDP_PE_STATES = {"reachable": L.MDP_PE_REACHABLE, "all": L.MDP_PE_ALL}
+
+    def mdp_policy_evaluation(self, dst, used, valid, rew, prg, prb, point, policy, *, theta,
+                              discount=1.0, max_iter=0, states="reachable", start_state=None,
+                              start_prob=None, path="auto"):
+        """Policy evaluation on the device (cpr_mdp_policy_evaluation) for E evaluations over P
+        points of one topology (the arrays of ``mdp_value_iteration``): ``point`` [E] indexes
+        the points, ``policy`` [E][S] holds the action slot a state plays or -1.
+        ``states="reachable"`` evaluates the states reached from ``start_state`` [E][n] with
+        ``start_prob`` [E][n] > 0 (one row [n] serves every evaluation), ``"all"`` every state.
+        ``max_iter`` 0: until delta < theta. Returns a dict of reward, progress [E][S], iter,
+        delta, status [E], path_used ("resident" / "global") and kernel_ms. Invalid input
+        raises ``CprError`` before anything is launched."""
+        m, keep = self._mdp_c(dst, used, valid, rew, prg, prb)
+        S = m.S
+        point = np.ascontiguousarray(point, dtype=np.int32)
+        policy = np.asarray(policy)
+        if policy.dtype.kind not in "iu":
+            raise ValueError("policy: expected an integer array")
+        # an entry beyond int32 names no slot either way: keep it refused after the cast
+        policy = np.ascontiguousarray(np.clip(policy, -1, 2 ** 31 - 1), dtype=np.int32)
+        if policy.ndim == 1:
+            policy = policy[None]
+        E = policy.shape[0]
+        if point.ndim != 1 or policy.ndim != 2 or policy.shape[1] != S or point.shape[0] != E:
+            raise ValueError("expected point [E] and policy [E][S]")
         if path not in self.MDP_VI_PATHS:
             raise ValueError(f"path: expected one of {sorted(self.MDP_VI_PATHS)}")
-        m = L.MdpC(S, A, T, P, dst.ctypes.data, used.ctypes.data, valid.ctypes.data,
-                   rew.ctypes.data, prg.ctypes.data, prb.ctypes.data)
-        o = L.MdpViOptsC(float(stop_delta), float(discount), int(max_iter),
-                         self.MDP_VI_PATHS[path])
-        out = dict(value=np.zeros((P, S)), progress=np.zeros((P, S)),
-                   policy=np.zeros((P, S), np.int32), iter=np.zeros(P, np.int64),
-                   delta=np.zeros(P), status=np.zeros(P, np.int32))
-        r = L.MdpViResultC(*(out[k].ctypes.data for k in
-                             ("value", "progress", "policy", "iter", "delta", "status")))
-        L.check(L.lib().cpr_mdp_value_iteration(self.handle, ctypes.byref(m), ctypes.byref(o),
-                                                ctypes.byref(r)))
+        if states not in self.MDP_PE_STATES:
+            raise ValueError(f"states: expected one of {sorted(self.MDP_PE_STATES)}")
+        n_start, ss, sp = 0, None, None
+        if states == "reachable":
+            if start_state is None or start_prob is None:
+                raise ValueError('states="reachable" needs start_state and start_prob')
+            ss = np.asarray(start_state)
+            if ss.dtype.kind not in "iu":
+                raise ValueError("start_state: expected an integer array")
+            ss = np.clip(ss, -1, 2 ** 31 - 1).astype(np.int32)
+            sp = np.asarray(start_prob, dtype=np.float64)
+            if ss.ndim == 1:
+                ss, sp = np.tile(ss, (E, 1)), np.tile(sp, (E, 1))
+            ss, sp = np.ascontiguousarray(ss), np.ascontiguousarray(sp)
+            if ss.ndim != 2 or ss.shape[0] != E or sp.shape != ss.shape:
+                raise ValueError("expected start_state and start_prob [E][n] or [n]")
+            n_start = ss.shape[1]
+        job = L.MdpPeC(E, point.ctypes.data, policy.ctypes.data, self.MDP_PE_STATES[states],
+                       n_start, ss.ctypes.data if ss is not None else None,
+                       sp.ctypes.data if sp is not None else None)
+        o = L.MdpPeOptsC(float(theta), float(discount), int(max_iter), self.MDP_VI_PATHS[path])
+        out = dict(reward=np.zeros((E, S)), progress=np.zeros((E, S)),
+                   iter=np.zeros(E, np.int64), delta=np.zeros(E), status=np.zeros(E, np.int32))
+        r = L.MdpPeResultC(*(out[k].ctypes.data for k in
+                             ("reward", "progress", "iter", "delta", "status")))
+        L.check(L.lib().cpr_mdp_policy_evaluation(self.handle, ctypes.byref(m), ctypes.byref(job),
+                                                  ctypes.byref(o), ctypes.byref(r)))
+        del keep
         out["path_used"] = "resident" if r.path_used == L.MDP_VI_RESIDENT else "global"
         out["kernel_ms"] = r.kernel_ms
         return out

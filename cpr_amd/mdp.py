@@ -212,6 +212,24 @@ def value_iteration_device(tabs, *, stop_delta, discount=1.0, max_iter=0, path="
     ``vi_kernel_ms`` (the whole call's)."""
     from . import device
 
+    single, ms = _one_topology(tabs)
+    first = ms[0]
+    used = np.asarray(first["used"], bool)
+    ctx = ctx or device.default_context()
+    r = ctx.mdp_value_iteration(first["dst"], used, first["valid"], first["rew"], first["prg"],
+                                np.stack([np.asarray(m["prb"], np.float64) for m in ms]),
+                                stop_delta=stop_delta, discount=discount, max_iter=max_iter,
+                                path=path)
+    out = [dict(vi_policy=r["policy"][p].astype(np.int64), vi_value=r["value"][p],
+                vi_progress=r["progress"][p], vi_iter=int(r["iter"][p]),
+                vi_delta=float(r["delta"][p]), vi_status=int(r["status"][p]),
+                vi_path=r["path_used"], vi_kernel_ms=r["kernel_ms"])
+           for p in range(len(ms))]
+    return out[0] if single else out
+
+
+def _one_topology(tabs):
+    """(single, packed MDPs) of one MDP or a list of MDPs, which must share a topology."""
     single = _is_single(tabs)
     ms = [_packed(tabs)] if single else [_packed(t) for t in tabs]
     if not ms:
@@ -229,17 +247,180 @@ def value_iteration_device(tabs, *, stop_delta, discount=1.0, max_iter=0, path="
                              "destinations, rewards and progress must agree)")
     if np.asarray(first["dst"]).size == 0:
         raise ValueError("an MDP needs at least one state, action slot and transition slot")
+    return single, ms
+
+
+# ---- policy evaluation (explicit_mdp.py:179-208, 328-378)
+
+def _checked_policy(m, policy):
+    """``policy`` as an int64 array over the states of the packed MDP ``m``; an entry >= 0 must
+    name an action slot its state offers (the reference raises IndexError only where it
+    happens to reach such a state; here it is a ValueError wherever it stands)."""
+    valid = np.asarray(m["valid"], bool)
+    n, n_act = valid.shape
+    policy = np.asarray(policy)
+    if policy.shape != (n,) or policy.dtype.kind not in "iu":
+        raise ValueError(f"policy: expected {n} integers, one action slot (or -1) per state")
+    policy = policy.astype(np.int64)
+    bad = policy >= n_act
+    ok = (policy >= 0) & ~bad
+    bad[ok] = ~valid[np.nonzero(ok)[0], policy[ok]]
+    if bad.any():
+        s = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"policy: state {s} does not offer action slot {int(policy[s])}")
+    return policy
+
+
+def _checked_start(start, n):
+    if start is None:  # compile_mdp numbers model.start() 0 and 1
+        start = [(s, 1.0) for s in range(min(2, n))]
+    start = [(int(s), float(p)) for s, p in start]
+    if not start:
+        raise ValueError("start: expected at least one (state id, probability)")
+    for s, _p in start:
+        if not 0 <= s < n:
+            raise ValueError(f"start: state {s} is outside [0, {n})")
+    return start
+
+
+def reachable_states(tab, policy, start=None):
+    """explicit_mdp.py:179-208: the set of states that ``policy`` reaches from the start states
+    with probability > 0 (``start``: a list of (state id, probability); default ids 0 and 1, as
+    ``compile_mdp`` numbers ``model.start()``, both counted), following ``tab[s][policy[s]]``.
+    Transitions with probability exactly 0 are skipped; a state with ``policy[s] < 0`` is a
+    leaf. ``tab`` may be a packed MDP."""
+    m = _packed(tab)
+    policy = _checked_policy(m, policy)
+    used = np.asarray(m["used"], bool)
+    dst, prb = np.asarray(m["dst"]), np.asarray(m["prb"])
+    todo = [s for s, p in _checked_start(start, len(policy)) if p > 0]
+    reachable = set(todo)
+    while todo:
+        s = todo.pop()
+        a = policy[s]
+        if a < 0:
+            continue
+        for j in np.nonzero(used[s, a] & (prb[s, a] != 0.0))[0]:
+            d = int(dst[s, a, j])
+            if d not in reachable:
+                reachable.add(d)
+                todo.append(d)
+    return reachable
+
+
+def policy_evaluation(tab, policy, *, theta, discount=1.0, start=None, states="reachable",
+                      max_iter=None):
+    """explicit_mdp.py:328-378 vectorised over states, bit for bit its results. The included
+    states are those ``reachable_states(tab, policy, start)`` gives (``states="reachable"``,
+    the reference's ``around_state=None``) or all of them (``states="all"``, the reference's
+    ``around_state`` given, whatever its value). Sweep i (from 1) computes, for every included
+    state with ``policy[s] >= 0``, r += prb * (rew + discount * reward_prev[dst]) and p
+    likewise over the transitions of ``tab[s][policy[s]]`` in their order (f64, one rounding
+    per operation); every other state stays 0 in reward and progress. delta is the largest
+    ``|new - old|`` of the reward vector over all states.
+
+    The reference's quirks are kept: the run stops when ``delta < theta`` (strict, where value
+    iteration stops at ``<=``), and only then asks whether ``max_iter`` is set and
+    ``i >= max_iter``, so a run that converges in its last allowed sweep counts as converged
+    and ``max_iter=0`` stops after the first sweep; a state outside the included set
+    contributes 0 to its predecessors for ever, also with ``states="all"`` and a policy of -1.
+    Unlike the reference, a ``policy[s]`` that names a slot its state does not offer is a
+    ``ValueError`` (there: an IndexError, and only if the state is reached).
+
+    Returns ``pe_reward``, ``pe_progress``, ``pe_iter`` and ``pe_delta``. ``tab`` may be a
+    packed MDP, as for ``value_iteration``."""
+    m = _packed(tab)
+    policy = _checked_policy(m, policy)
+    if states not in ("reachable", "all"):
+        raise ValueError('states: expected "reachable" or "all"')
+    if not theta >= 0:
+        raise ValueError("theta must be >= 0")
+    if theta == 0 and max_iter is None:
+        raise ValueError("infinite iteration: theta == 0 and no max_iter")
+    n = len(policy)
+    included = np.ones(n, bool)
+    if states == "reachable":
+        included[:] = False
+        included[list(reachable_states(m, policy, start))] = True
+    act = included & (policy >= 0)
+    rows, slot = np.arange(n), np.where(act, policy, 0)
+    used = np.asarray(m["used"], bool)[rows, slot] & act[:, None]
+    dst = np.where(used, np.asarray(m["dst"])[rows, slot], 0)
+    prb = np.where(used, np.asarray(m["prb"], np.float64)[rows, slot], 0.0)
+    rew = np.where(used, np.asarray(m["rew"], np.float64)[rows, slot], 0.0)
+    prg = np.where(used, np.asarray(m["prg"], np.float64)[rows, slot], 0.0)
+    reward = np.zeros(n)
+    progress = np.zeros(n)
+    i = 1
+    while True:
+        r = np.zeros(n)
+        p = np.zeros(n)
+        for j in range(dst.shape[1]):  # += in transition order, as the reference's inner loop
+            tr = prb[:, j] * (rew[:, j] + discount * reward[dst[:, j]])
+            tp = prb[:, j] * (prg[:, j] + discount * progress[dst[:, j]])
+            r = np.where(used[:, j], r + tr, r)
+            p = np.where(used[:, j], p + tp, p)
+        delta = float(np.abs(r - reward).max()) if n else 0.0
+        reward, progress = r, p
+        if delta < theta:
+            break
+        if max_iter is not None and i >= max_iter:
+            break
+        i += 1
+    return dict(pe_reward=reward, pe_progress=progress, pe_iter=i, pe_delta=delta)
+
+
+def policy_evaluation_device(tabs, policies, pairs=None, *, theta, discount=1.0, start=None,
+                             states="reachable", max_iter=None, path="auto", ctx=None):
+    """``policy_evaluation`` on the device (``device.Context.mdp_policy_evaluation``) for
+    Q policies x P points in one call. ``tabs``: one MDP or a list of MDPs that share a
+    topology (as for ``value_iteration_device``), the points; ``policies``: [Q][S]; ``pairs``:
+    a list of (policy index, point index), by default the full cross product, policy-major.
+    ``start``: as for ``policy_evaluation``, one list for every evaluation or one list per
+    point (the start probabilities of a model depend on its alpha). ``max_iter``: None or
+    >= 1. Returns one dict per pair with the host's keys, bit for bit its results, plus
+    ``pe_status`` (0 converged, 1 stopped at max_iter, 2 not converged at the library's sweep
+    cap), ``pe_path`` and ``pe_kernel_ms`` (the whole call's)."""
+    from . import device
+
+    _single, ms = _one_topology(tabs)
+    first = ms[0]
+    n = np.shape(first["dst"])[0]
+    policies = [_checked_policy(first, p) for p in policies]
+    if not policies:
+        raise ValueError("no policy to evaluate")
+    if pairs is None:
+        pairs = [(q, p) for q in range(len(policies)) for p in range(len(ms))]
+    pairs = [(int(q), int(p)) for q, p in pairs]
+    if not pairs:
+        raise ValueError("no (policy, point) pair to evaluate")
+    for q, p in pairs:
+        if not 0 <= q < len(policies) or not 0 <= p < len(ms):
+            raise ValueError(f"pair ({q}, {p}): no such policy or point")
+    if states not in ("reachable", "all"):
+        raise ValueError('states: expected "reachable" or "all"')
+    if max_iter is not None and max_iter < 1:
+        raise ValueError("max_iter: expected None or at least 1")
+    if start is not None and _nesting(list(start)) == 3:
+        if len(start) != len(ms):
+            raise ValueError("start: expected one list per point")
+        starts = [_checked_start(s, n) for s in start]
+    else:
+        starts = [_checked_start(start, n)] * len(ms)
+    if len({len(s) for s in starts}) != 1:
+        raise ValueError("start: every point needs the same number of start states")
     ctx = ctx or device.default_context()
-    r = ctx.mdp_value_iteration(first["dst"], used, first["valid"], first["rew"], first["prg"],
-                                np.stack([np.asarray(m["prb"], np.float64) for m in ms]),
-                                stop_delta=stop_delta, discount=discount, max_iter=max_iter,
-                                path=path)
-    out = [dict(vi_policy=r["policy"][p].astype(np.int64), vi_value=r["value"][p],
-                vi_progress=r["progress"][p], vi_iter=int(r["iter"][p]),
-                vi_delta=float(r["delta"][p]), vi_status=int(r["status"][p]),
-                vi_path=r["path_used"], vi_kernel_ms=r["kernel_ms"])
-           for p in range(len(ms))]
-    return out[0] if single else out
+    r = ctx.mdp_policy_evaluation(
+        first["dst"], first["used"], first["valid"], first["rew"], first["prg"],
+        np.stack([np.asarray(m["prb"], np.float64) for m in ms]),
+        [p for _q, p in pairs], np.stack([policies[q] for q, _p in pairs]),
+        theta=theta, discount=discount, max_iter=0 if max_iter is None else max_iter,
+        states=states, start_state=[[s for s, _ in starts[p]] for _q, p in pairs],
+        start_prob=[[pr for _, pr in starts[p]] for _q, p in pairs], path=path)
+    return [dict(pe_reward=r["reward"][e], pe_progress=r["progress"][e],
+                 pe_iter=int(r["iter"][e]), pe_delta=float(r["delta"][e]),
+                 pe_status=int(r["status"][e]), pe_path=r["path_used"],
+                 pe_kernel_ms=r["kernel_ms"]) for e in range(len(pairs))]
 
 
 def _nesting(x):
@@ -497,3 +678,126 @@ def fc16_policy_value(alpha, gamma, horizon, table, *, max_states=200_000):
     v_r = np.linalg.solve(m, rhs_r)
     v_g = np.linalg.solve(m, rhs_g)
     return (pa * v_r[0] + (1 - pa) * v_r[1], pa * v_g[0] + (1 - pa) * v_g[1])
+
+
+# ---- table policies as MDP policies, and the revenue of Q policies at P points
+
+def fc16_honest_table(dim):
+    """Honest play as a `CPR_FC16_POLICY_TABLE` (fc16_lane.h ``POLICY_HONEST``)."""
+    table = np.zeros((dim, dim, 3), np.uint8)
+    for a in range(dim):
+        for h in range(dim):
+            table[a, h, :] = FC16_OVERRIDE if a > h else (FC16_ADOPT if h > a else FC16_WAIT)
+    return table.ravel()
+
+
+def fc16_sm1_table(dim):
+    """SM1 (sapirshtein-2016-sm1) as a `CPR_FC16_POLICY_TABLE` (fc16_lane.h ``POLICY_SM1``)."""
+    table = np.zeros((dim, dim, 3), np.uint8)
+    for a in range(dim):
+        for h in range(dim):
+            if h > a:
+                x = FC16_ADOPT
+            elif h == 1 and a == 1:
+                x = FC16_MATCH
+            elif h == a - 1 and h >= 1:
+                x = FC16_OVERRIDE
+            else:
+                x = FC16_WAIT
+            table[a, h, :] = x
+    return table.ravel()
+
+
+_FC16_MODEL = {name: act for act, name in _FC16_NAME.items()}
+
+
+def mdp_policy_from_table(model, states, table, kind):
+    """The MDP policy that a table plays: per state of ``states`` (``compile_mdp``'s order)
+    the index of the table's action in ``model.actions(state)``, and a final -1 for the
+    terminal state that ``ptmdp`` appends.
+
+    ``kind="nakamoto"``: a `CPR_POLICY_TABLE` over (h, a, event), event = Network (1) for
+    fork RELEVANT and ProofOfWork (0) for IRRELEVANT and ACTIVE, as ``policy_table`` writes
+    it. ``kind="fc16"``: a `CPR_FC16_POLICY_TABLE` over (a, h, fork) with the env's legality
+    rule (``fc16_policy_value``: Override without a > h and Match without a >= h act as
+    Wait). a and h beyond the table read its last row or column. An action the model does
+    not offer in a state (Wait at a truncated state, Match without a relevant fork, ...)
+    becomes Override if a > h, else Adopt."""
+    table = np.asarray(table, np.uint8).ravel()
+    if kind == "nakamoto":
+        dim = int(round((table.size // 2) ** 0.5))
+        if dim < 1 or dim * dim * 2 != table.size:
+            raise ValueError("table: expected dim * dim * 2 entries")
+    elif kind == "fc16":
+        dim = int(round((table.size // 3) ** 0.5))
+        if dim < 1 or dim * dim * 3 != table.size:
+            raise ValueError("table: expected dim * dim * 3 entries")
+    else:
+        raise ValueError('kind: expected "nakamoto" or "fc16"')
+    if table.max() > 3:
+        raise ValueError("table: an entry is no action")
+    policy = np.full(len(states) + 1, -1, np.int64)
+    for sid, (a, h, fork) in enumerate(states):
+        acts = model.actions((a, h, fork))
+        ca, ch = min(a, dim - 1), min(h, dim - 1)
+        if kind == "nakamoto":
+            x = int(table[(ch * dim + ca) * 2 + (1 if fork == RELEVANT else 0)])
+        else:
+            x = int(table[(ca * dim + ch) * 3 + fork])
+            if (x == FC16_OVERRIDE and not a > h) or (x == FC16_MATCH and not a >= h):
+                x = FC16_WAIT
+            x = _FC16_MODEL[x]
+        if x not in acts:
+            x = OVERRIDE if a > h else ADOPT
+        policy[sid] = acts.index(x)
+    return policy
+
+
+def revenue_matrix(alphas, gammas, policies=None, *, maximum_fork_length=20, horizon=100,
+                   stop_delta=1e-6, theta=1e-6, ctx=None):
+    """The PTO revenue of Q policies at P = len(alphas) * len(gammas) points (alpha-major), all
+    evaluations in one ``policy_evaluation_device`` call after one ``solve_grid``: every
+    point's optimum, honest play, SM1 and the tables of ``policies`` (a dict label -> (table,
+    kind) or a list of (table, kind), ``kind`` as for ``mdp_policy_from_table``), each
+    evaluated at every point over the states it reaches from the model's start states.
+    revenue = sum start * pe_reward / sum start * pe_progress over the start states.
+
+    Returns a dict: ``revenue`` [Q][P]; ``policies`` (Q labels: "optimum(alpha,gamma)" per
+    point, "honest", "sm1", then the given ones) and ``points`` (P (alpha, gamma) pairs);
+    ``vi_revenue`` [P], the same ratio of the optimum's own value-iteration vectors;
+    ``pe_iter`` and ``pe_status`` [Q][P]."""
+    solved = solve_grid(alphas, gammas, maximum_fork_length=maximum_fork_length,
+                        horizon=horizon, stop_delta=stop_delta, ctx=ctx)
+    points = [(m.alpha, m.gamma) for m, _s, _v in solved]
+    model, states, _vi = solved[0]  # the topology does not depend on the point
+    tabs = [pack(ptmdp(compile_mdp(m)[1], horizon)) for m, _s, _v in solved]
+    starts = [[(0, m.start()[0][1]), (1, m.start()[1][1])] for m, _s, _v in solved]
+    labels = [f"optimum({a:g},{g:g})" for a, g in points] + ["honest", "sm1"]
+    pols = [np.asarray(vi["vi_policy"], np.int64) for _m, _s, vi in solved]
+    dim = maximum_fork_length + 1
+    given = list(policies.items()) if isinstance(policies, dict) else \
+        [(f"table{i}", tk) for i, tk in enumerate(policies or [])]
+    for table in (fc16_honest_table(dim), fc16_sm1_table(dim)):
+        pols.append(mdp_policy_from_table(model, states, table, "fc16"))
+    for label, (table, kind) in given:
+        pols.append(mdp_policy_from_table(model, states, table, kind))
+        labels.append(label)
+    pes = policy_evaluation_device(tabs, pols, theta=theta, start=starts, ctx=ctx)
+    n_p = len(points)
+
+    def ratio(reward, progress, start):
+        num = sum(p * reward[s] for s, p in start)
+        den = sum(p * progress[s] for s, p in start)
+        return num / den if den else 0.0
+
+    revenue = np.zeros((len(pols), n_p))
+    iters = np.zeros((len(pols), n_p), np.int64)
+    status = np.zeros((len(pols), n_p), np.int32)
+    for e, pe in enumerate(pes):
+        q, p = divmod(e, n_p)
+        revenue[q, p] = ratio(pe["pe_reward"], pe["pe_progress"], starts[p])
+        iters[q, p], status[q, p] = pe["pe_iter"], pe["pe_status"]
+    vi_revenue = np.array([ratio(vi["vi_value"], vi["vi_progress"], starts[p])
+                           for p, (_m, _s, vi) in enumerate(solved)])
+    return dict(revenue=revenue, policies=labels, points=points, vi_revenue=vi_revenue,
+                pe_iter=iters, pe_status=status)

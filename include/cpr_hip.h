@@ -1070,6 +1070,70 @@ typedef struct cpr_mdp_vi_result {
 int cpr_mdp_value_iteration(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_vi_opts* opts,
                             cpr_mdp_vi_result* result);
 
+/* Policy evaluation over explicit MDPs (additive within ABI v11; mdp/lib/explicit_mdp.py:328-378
+ * and :179-208 on the device). A job holds E evaluations over one cpr_mdp: each
+ * plays its own policy at one of the P points. A cross product, a diagonal or a ragged selection
+ * of (policy, point) pairs are all this one form. Host pointers. */
+enum cpr_mdp_pe_states {
+  CPR_MDP_PE_REACHABLE = 0, /* the states the policy reaches from the start states (the
+                               reference's around_state = None) */
+  CPR_MDP_PE_ALL = 1        /* every state (the reference's around_state given) */
+};
+enum cpr_mdp_pe_status {
+  CPR_MDP_PE_CONVERGED = 0,    /* the last sweep's delta < theta */
+  CPR_MDP_PE_MAX_ITER = 1,     /* stopped after sweep max_iter */
+  CPR_MDP_PE_NOT_CONVERGED = 2 /* max_iter == 0 and the library's sweep cap was reached: 2^20,
+                                  or the lower value of the environment variable
+                                  CPR_MDP_PE_SWEEP_CAP (a test hook) */
+};
+
+typedef struct cpr_mdp_pe {
+  int64_t E;                  /* evaluations, >= 1 */
+  const int32_t* point;       /* [E] index into the P probability arrays */
+  const int32_t* policy;      /* [E][S] the action slot played, negative: none (a leaf) */
+  int32_t states;             /* enum cpr_mdp_pe_states */
+  int32_t n_start;            /* start states per evaluation (REACHABLE: >= 1; ALL: unused) */
+  const int32_t* start_state; /* [E][n_start] */
+  const double* start_prob;   /* [E][n_start] a start state counts if its probability is > 0 */
+} cpr_mdp_pe;
+
+typedef struct cpr_mdp_pe_opts {
+  double theta;     /* >= 0 */
+  double discount;  /* in (0, 1] */
+  int64_t max_iter; /* >= 0; 0: until delta < theta (then theta must be > 0) */
+  int32_t path;     /* enum cpr_mdp_vi_path; AUTO: resident if the states fit one workgroup and
+                       its estimated sweep time is the lower one */
+} cpr_mdp_pe_opts;
+/* theta 1e-6, discount 1, max_iter 0, path AUTO */
+int cpr_mdp_pe_opts_default(cpr_mdp_pe_opts* opts);
+
+typedef struct cpr_mdp_pe_result {
+  double* reward;    /* [E][S] */
+  double* progress;  /* [E][S] */
+  int64_t* iter;     /* [E] sweeps done */
+  double* delta;     /* [E] max |reward - previous reward| of the last sweep */
+  int32_t* status;   /* [E] enum cpr_mdp_pe_status */
+  int32_t path_used; /* CPR_MDP_VI_RESIDENT or CPR_MDP_VI_GLOBAL */
+  double kernel_ms;  /* HIP events around the launches, the status reads between them included */
+} cpr_mdp_pe_result;
+
+/* Per evaluation: the included states are found on the host before anything is launched (from
+ * the start states with probability > 0 along the policy's used slots whose probability at the
+ * evaluation's point is not exactly 0; a state with a negative policy entry is a leaf), or are
+ * all states. reward = progress = 0; sweep i computes, for every included state with a policy
+ * entry >= 0, r += prb (rew + discount reward[dst]) and p likewise over the used slots of that
+ * action in slot order (f64, one rounding per operation); every other state stays 0. The
+ * evaluation stops after sweep i if delta < theta (strict, unlike value iteration), else if
+ * max_iter > 0 and i >= max_iter; evaluations stop independently. Every array of `result` is
+ * filled. Checked before anything is launched (CPR_E_INVALID_ARG): what cpr_mdp_value_iteration
+ * checks of `mdp`, E < 1, NULL arrays, a point outside [0, P), a policy entry >= A or one that
+ * names an action with valid == 0 (at any state, reached or not), states REACHABLE with
+ * n_start < 1 or a start state outside [0, S), an unknown `states`, discount outside (0, 1],
+ * theta < 0, max_iter < 0, theta == 0 with max_iter == 0, an unknown path. CPR_E_CAPACITY: as
+ * for value iteration. */
+int cpr_mdp_policy_evaluation(cpr_ctx* ctx, const cpr_mdp* mdp, const cpr_mdp_pe* job,
+                              const cpr_mdp_pe_opts* opts, cpr_mdp_pe_result* result);
+
 #ifdef __cplusplus
 }
 #endif

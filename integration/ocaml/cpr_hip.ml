@@ -414,6 +414,16 @@ let mdp_value_iteration =
     (ptr ctx @-> ptr void @-> ptr void @-> ptr void @-> returning int)
 ;;
 
+(* policy evaluation over explicit MDPs (added within ABI v11): cpr_mdp, cpr_mdp_pe,
+   cpr_mdp_pe_opts and cpr_mdp_pe_result are untyped pointers to caller-built C structs *)
+let mdp_pe_opts_default = foreign "cpr_mdp_pe_opts_default" (ptr void @-> returning int)
+
+let mdp_policy_evaluation =
+  foreign
+    "cpr_mdp_policy_evaluation"
+    (ptr ctx @-> ptr void @-> ptr void @-> ptr void @-> ptr void @-> returning int)
+;;
+
 (* errors: every entry point returns a status; non-zero becomes the exception the
    reference raises at the same point (engine.ml:37-51 Failure, network.ml:63-72
    Invalid_argument) *)

@@ -2,7 +2,8 @@
 greedy policy of the Q-network tabulated after every iteration (mdp.fc16_table_from_net) and
 the table's exact expected episode reward (mdp.fc16_policy_value: no Monte Carlo noise)
 recorded beside the exact values of honest play, SM1 and the value-iteration table. The DQN
-twin of tools/fc16_ppo_vs_optimum.py, with the same env, table and border.
+twin of tools/fc16_ppo_vs_optimum.py, with the same env, table and border, and the same
+`pto_revenue` beside it (the table as a policy of the PTO-mapped MDP, evaluated on the device).
 
 alpha .4, gamma .5, horizon 25. dqn.yml's FC16SSZwPT-v0 hyperparameters (cpr_amd.dqn.FC16_PRESET:
 batch 500, 100 gradient steps per iteration, lr 1e-3, discount 1, tau 0.01, epsilon 1 -> 0.1
@@ -82,15 +83,35 @@ res = dict(setup=dict(alpha=ALPHA, gamma=GAMMA, horizon=HORIZON, lanes=args.lane
                       epsilon=[preset["exploration_initial_eps"], preset["exploration_final_eps"],
                                preset["exploration_fraction"]],
                       table_dim=DIM, border="honest play where a or h = dim - 1"))
-res["honest"] = value(table_of(honest))
-res["sm1"] = value(with_honest_border(table_of(sm1)))
 vi = mdp.fc16_table(ALPHA, GAMMA, dim=DIM, maximum_fork_length=DIM - 1, horizon=HORIZON)
-res["value_iteration"] = value(with_honest_border(vi))
+FIXED = dict(honest=table_of(honest), sm1=with_honest_border(table_of(sm1)),
+             value_iteration=with_honest_border(vi))
+for name, fixed in FIXED.items():
+    res[name] = value(fixed)
+
+# the other measure: the table mapped onto the PTO-mapped MDP of the same cut-off
+MODEL = mdp.BitcoinSM(ALPHA, GAMMA, DIM - 1)
+STATES, TAB = mdp.compile_mdp(MODEL)
+PTO = mdp.pack(mdp.ptmdp(TAB, HORIZON))
+START = [(sid, p) for sid, (_s, p) in enumerate(MODEL.start())]
+
+
+def pto_revenue(table, ctx):
+    """Reward over progress of the table's MDP policy from the model's start states. A table
+    that earns nothing stops in its first sweep (the stop asks the reward's delta alone), with
+    no progress at the start states yet: 0, as mdp.revenue_matrix has it."""
+    policy = mdp.mdp_policy_from_table(MODEL, STATES, table, "fc16")
+    pe = mdp.policy_evaluation_device(PTO, [policy], theta=1e-6, start=START, ctx=ctx)[0]
+    reward = sum(p * pe["pe_reward"][s] for s, p in START)
+    progress = sum(p * pe["pe_progress"][s] for s, p in START)
+    return float(reward / progress) if progress else 0.0
 
 
 def main():
     """The GPU part. The batch and the context are closed before the interpreter exits."""
     ctx = device.Context(0)
+    for name, fixed in FIXED.items():
+        res[name]["pto_revenue"] = pto_revenue(fixed, ctx)
     cfg, keep = device.make_config(protocol=L.PROTO_FC16_ENV, alpha=ALPHA, gamma=GAMMA,
                                    horizon=HORIZON, max_steps=254, seed=args.seed,
                                    n_lanes=args.lanes, policy=L.FC16_POLICY_HONEST)
@@ -109,12 +130,14 @@ def main():
     b.dqn_init(args.capacity)
     eps = dqn.epsilon_schedule(preset["exploration_initial_eps"], preset["exploration_final_eps"],
                                preset["exploration_fraction"])
-    curve = [dict(iteration=0, **value(with_honest_border(
-        mdp.fc16_table_from_net(b.get_policy_net(), DIM, ctx=ctx))))]
+    table = with_honest_border(mdp.fc16_table_from_net(b.get_policy_net(), DIM, ctx=ctx))
+    curve = [dict(iteration=0, **value(table), pto_revenue=pto_revenue(table, ctx))]
     run = dqn.train(b, args.iterations, args.steps, opts, epsilon=eps)
     for it, (summary, stats) in enumerate(run, 1):
-        row = value(with_honest_border(mdp.fc16_table_from_net(b.get_policy_net(), DIM, ctx=ctx)))
-        row.update(iteration=it, episodes=int(summary.episodes), epsilon=stats["epsilon"],
+        table = with_honest_border(mdp.fc16_table_from_net(b.get_policy_net(), DIM, ctx=ctx))
+        row = value(table)
+        row.update(pto_revenue=pto_revenue(table, ctx), iteration=it,
+                   episodes=int(summary.episodes), epsilon=stats["epsilon"],
                    gradient_steps=stats["n_steps"], loss=stats["loss"], q=stats["q"])
         curve.append(row)
         print(f"# {it}: E[reward] {row['reward']:.4f}  (honest {res['honest']['reward']:.4f}, sm1 "

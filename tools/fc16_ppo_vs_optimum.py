@@ -1,7 +1,9 @@
 """The device learner against ground truth: PPO on the FC16 env (CPR_PROTO_FC16_ENV), the
 network tabulated after every iteration (mdp.fc16_table_from_net) and the table's exact
 expected episode reward (mdp.fc16_policy_value: no Monte Carlo noise) recorded beside the exact
-values of honest play, SM1 and the value-iteration table.
+values of honest play, SM1 and the value-iteration table. Every row also has `pto_revenue`: the
+same table as a policy of the PTO-mapped MDP (mdp.mdp_policy_from_table), reward over progress
+from the start states by mdp.policy_evaluation_device; DESIGN.md 4.8 tells the two apart.
 
 alpha .4, gamma .5, horizon 25. The network is tabulated for a, h < --dim; on the table's
 border (a or h = dim - 1) honest play replaces the network's action, as the MDP's
@@ -72,16 +74,36 @@ res = dict(setup=dict(alpha=ALPHA, gamma=GAMMA, horizon=HORIZON, lanes=args.lane
                       steps_per_iteration=args.steps, iterations=args.iterations,
                       network=f"{args.depth}x{args.width}", lr=args.lr, table_dim=DIM,
                       border="honest play where a or h = dim - 1"))
-res["honest"] = value(table_of(honest))
-res["sm1"] = value(with_honest_border(table_of(sm1)))
 vi = mdp.fc16_table(ALPHA, GAMMA, dim=DIM, maximum_fork_length=DIM - 1, horizon=HORIZON)
-res["value_iteration"] = value(with_honest_border(vi))
+FIXED = dict(honest=table_of(honest), sm1=with_honest_border(table_of(sm1)),
+             value_iteration=with_honest_border(vi))
+for name, fixed in FIXED.items():
+    res[name] = value(fixed)
+
+# the other measure: the table mapped onto the PTO-mapped MDP of the same cut-off
+MODEL = mdp.BitcoinSM(ALPHA, GAMMA, DIM - 1)
+STATES, TAB = mdp.compile_mdp(MODEL)
+PTO = mdp.pack(mdp.ptmdp(TAB, HORIZON))
+START = [(sid, p) for sid, (_s, p) in enumerate(MODEL.start())]
+
+
+def pto_revenue(table, ctx):
+    """Reward over progress of the table's MDP policy from the model's start states. A table
+    that earns nothing stops in its first sweep (the stop asks the reward's delta alone), with
+    no progress at the start states yet: 0, as mdp.revenue_matrix has it."""
+    policy = mdp.mdp_policy_from_table(MODEL, STATES, table, "fc16")
+    pe = mdp.policy_evaluation_device(PTO, [policy], theta=1e-6, start=START, ctx=ctx)[0]
+    reward = sum(p * pe["pe_reward"][s] for s, p in START)
+    progress = sum(p * pe["pe_progress"][s] for s, p in START)
+    return float(reward / progress) if progress else 0.0
 
 
 def main():
     """The GPU part. The batch and the context are closed before the interpreter exits, as
     bench.py closes its own: nothing of the library is left to module teardown."""
     ctx = device.Context(0)
+    for name, fixed in FIXED.items():
+        res[name]["pto_revenue"] = pto_revenue(fixed, ctx)
     cfg, keep = device.make_config(protocol=L.PROTO_FC16_ENV, alpha=ALPHA, gamma=GAMMA,
                                    horizon=HORIZON, max_steps=254, seed=args.seed,
                                    n_lanes=args.lanes, policy=L.FC16_POLICY_HONEST)
@@ -99,11 +121,13 @@ def main():
                                       vf_head=lin(1, args.width)))
     opts = ppo.PPOOptions(n_epochs=4, minibatch=args.lanes * args.steps // 8, lr=args.lr,
                           ent_coef=0.01, gae_gamma=0.999, clip_range=0.2)
-    curve = [dict(iteration=0, **value(with_honest_border(
-        mdp.fc16_table_from_net(b.get_policy_net(), DIM, ctx=ctx))))]
+    table = with_honest_border(mdp.fc16_table_from_net(b.get_policy_net(), DIM, ctx=ctx))
+    curve = [dict(iteration=0, **value(table), pto_revenue=pto_revenue(table, ctx))]
     for it, (summary, stats) in enumerate(ppo.train(b, args.iterations, args.steps, opts), 1):
-        row = value(with_honest_border(mdp.fc16_table_from_net(b.get_policy_net(), DIM, ctx=ctx)))
-        row.update(iteration=it, fused=b.rollout_net_fused(), episodes=int(summary.episodes),
+        table = with_honest_border(mdp.fc16_table_from_net(b.get_policy_net(), DIM, ctx=ctx))
+        row = value(table)
+        row.update(pto_revenue=pto_revenue(table, ctx), iteration=it,
+                   fused=b.rollout_net_fused(), episodes=int(summary.episodes),
                    policy_loss=stats["policy_loss"], value_loss=stats["value_loss"])
         curve.append(row)
         print(f"# {it}: E[reward] {row['reward']:.4f}  (honest {res['honest']['reward']:.4f}, sm1 "

@@ -465,7 +465,12 @@ class Batch:
 
     def close(self):
         if self.handle:
-            L.lib().cpr_batch_destroy(self.handle)
+            # cpr_batch_destroy reads the batch's context (it launches what is pending there and
+            # waits for its stream): a batch that outlived its context, e.g. one a failed test
+            # left to the garbage collector after its fixture closed the context, is dropped
+            # without the call, since the context's memory is gone
+            if self.ctx.handle:
+                L.lib().cpr_batch_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

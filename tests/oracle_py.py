@@ -283,6 +283,63 @@ def run_episodes(config, first, n, threads=1):
     return rec
 
 
+def _isum(a):
+    """Sum of an integer array as a Python int (never a wrapped int64)."""
+    a = np.asarray(a)
+    if a.size == 0:
+        return 0
+    if a.size * max(1, int(np.abs(a).max())) < 1 << 62:
+        return int(a.sum(dtype=np.int64))
+    return sum(int(x) for x in a)
+
+
+def reduce_records(rec):
+    """The cpr_summary of an oracle record array as {field: int, "hist": [64 ints]}, by
+    include/cpr_hip.h's definition of each word and from the records' own columns: nothing of
+    the device's reduction (no reward taken from a height, no shared rounding helper).
+
+    Per valid episode: rel = reward_attacker / (reward_attacker + reward_defender), one
+    IEEE division, 0 where the sum is 0; the *_fx words add rint(x * 2^20), rel_revenue_fx
+    rint(rel * 2^32), rel_revenue_sq_fx rint(rel * rel * 2^32); orphans adds n_activations -
+    head_height; the histogram bin is int(rel * 64) clipped to 0..63; status_tie /
+    status_overlap count the bit, status_other any bit but TIE, OVERLAP and EXACT_RERUN. An
+    episode with CPR_ST_INVALID bits counts in steps, activations and invalid only. (The
+    numpy operations round like the scalar ones: one rounding per operation on doubles.)"""
+    from cpr_amd import _lib as C
+
+    rec = np.asarray(rec)
+    st = rec["status"].astype(np.int64)
+    ok = (st & C.ST_INVALID) == 0
+    out = {
+        "steps": _isum(rec["n_steps"]),
+        "activations": _isum(rec["n_activations"]),
+        "invalid": int(np.count_nonzero(~ok)),
+        "episodes": int(np.count_nonzero(ok)),
+    }
+    v = rec[ok]
+    st = st[ok]
+    ra = v["reward_attacker"].astype(np.float64)
+    rd = v["reward_defender"].astype(np.float64)
+    tot = ra + rd
+    rel = np.zeros(len(v), dtype=np.float64)
+    np.divide(ra, tot, out=rel, where=tot != 0.0)
+    fx = lambda x, scale: _isum(np.rint(x * scale).astype(np.int64))  # noqa: E731
+    out["reward_attacker_fx"] = fx(ra, 1048576.0)
+    out["reward_defender_fx"] = fx(rd, 1048576.0)
+    out["progress_fx"] = fx(v["progress"].astype(np.float64), 1048576.0)
+    # (below 2^63 per episode: rel <= 1 in every valid record; uint64 keeps the word's range)
+    out["rel_revenue_fx"] = _isum(np.rint(rel * 4294967296.0).astype(np.uint64))
+    out["rel_revenue_sq_fx"] = _isum(np.rint(rel * rel * 4294967296.0).astype(np.uint64))
+    out["orphans"] = _isum(v["n_activations"].astype(np.int64) - v["head_height"].astype(np.int64))
+    out["status_tie"] = int(np.count_nonzero(st & C.ST_TIE))
+    out["status_overlap"] = int(np.count_nonzero(st & C.ST_OVERLAP))
+    out["status_other"] = int(np.count_nonzero(
+        st & ~np.int64(C.ST_TIE | C.ST_OVERLAP | C.ST_EXACT_RERUN)))
+    bins = np.clip((rel * float(C.HIST_BINS)).astype(np.int64), 0, C.HIST_BINS - 1)
+    out["hist"] = [int(x) for x in np.bincount(bins, minlength=C.HIST_BINS)]
+    return out
+
+
 def export_traces(config, first, n, rng=None):
     """Run episodes [first, first + n) of `config` in the oracle, logging every draw:
     returns (cpr_amd._lib.Trace, records). rng=None draws from the keyed stream; an

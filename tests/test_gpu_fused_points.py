@@ -129,7 +129,9 @@ def test_group_sizes(torch, ctx, m):
     for s in got:
         assert s.episodes == N
     if m == NAMAX + 1:
-        # the record kernel's summary, which the parity tests pin to the oracle
+        # the record kernel's summary: one more device-to-device link (its records are what
+        # the parity tests compare with the oracle, its summary is reduced on the device).
+        # The fused path's own pin to the oracle is tests/test_gpu_sweep_oracle.py
         _assert_equal(got, [b.run(N, records=True)[0] for b in batches], "records")
     for b in batches:
         b.close()

@@ -1591,6 +1591,10 @@ static int fuse_lanes(int kind, int cap) {
 static int fuse_kind(const cpr_batch* b, const cpr_episode_record* rec_dev) {
   if (b->cfg.protocol != CPR_PROTO_NAKAMOTO || b->nak_ev || b->is_ev || b->is_eth) return 0;
   const int kind = run_episodes_fusable(b->P, b->cfg.mode, rec_dev != nullptr);
+  // k_run_episodes_fused makes no capacity test (LaneMem::cap_test): an episode's
+  // max_steps + 1 activations must fit below cap. nak_params always sizes cap so; this keeps
+  // the premise where it is relied on (a fusable launch has max_steps <= 2^14, lazy_clock_ok)
+  if (kind != 0 && (int64_t)b->P.cap < b->P.max_steps + 2) return 0;
   // the deferred-race group's second passes run on the side stream only (CPR_SIDE_PASS=0:
   // every call launches at once, its second pass on the stream)
   const char* sp = getenv("CPR_SIDE_PASS");

@@ -84,6 +84,9 @@ __global__ __launch_bounds__(kBlock) void k_run_episodes_fused(NakParams P, Seed
   M.replay.masks = nullptr;
   M.times = false;
   M.d2 = true;
+  // gym mode, one activation per step, and the launcher fuses only where cap >= max_steps + 2
+  // (capi.hip fuse_kind): the private chain cannot reach its capacity
+  M.cap_test = false;
   if constexpr (ARR != 0) {
     // each wave's race list, flags and episode words (as k_run_episodes, TT = 2)
     M.rq = rq + (threadIdx.x / WAVE) * (RQF * WAVE);

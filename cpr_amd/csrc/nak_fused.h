@@ -190,7 +190,15 @@ __host__ __device__ inline CPR_AI void fused_step_pre(LN (&L)[NA], const NakPara
                                                       const St& S, const LaneMem& M) {
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
-    L[i].apply(L[i].template policy_action<POL>(P));
+    if constexpr (LN::PK && POL >= P_HONEST && POL <= P_SM1) {
+      // packed tips: the policy's decisions as flags, no action code (policy_flags)
+      int32_t h, a, dd, ev;
+      L[i].observe(&h, &a, &dd, &ev);
+      const PolicyFlags f = policy_flags<POL>(h, a);
+      L[i].apply_flags(f.adopt, f.relx, f.ovr);
+    } else {
+      L[i].apply(L[i].template policy_action<POL>(P));
+    }
     L[i].template resolve<St, 0, ARR ? 2 : 1>(P, S, M);
   }
   if constexpr (ARR != 0) fused_enqueue_races<NA>(L, M);

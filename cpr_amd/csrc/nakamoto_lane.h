@@ -98,6 +98,11 @@ struct LaneMem {
   // defender masks (onA, the race masks) then live in their low words and the lane keeps
   // them there, so their 64-bit shifts, compares and selects in pairs become 32-bit ones
   bool d2 = false;
+  // the private chain's capacity is tested at every activation (ST_DEEP_FORK). A kernel whose
+  // launcher guarantees cap >= max_steps + 2 in gym mode sets a compile-time false (packed
+  // tips only: k_run_episodes_fused): activation index ka <= max_steps finds n <= ka, so
+  // n + 1 <= max_steps + 1 < cap and the test cannot fire
+  bool cap_test = true;
 };
 
 // deferred races: queue entries per lane of a wave (the list is the wave's: 64 times this)
@@ -288,6 +293,43 @@ __host__ __device__ inline CPR_AI int32_t nak_policy(int32_t policy, int32_t h, 
       return (int32_t)table[(hp * dim + ap) * 2 + ev];
     }
   }
+}
+
+// A built-in policy's action as the tests apply makes of it, straight from the observation:
+// adopt (A_ADOPT), relx (A_MATCH or A_OVERRIDE), ovr (A_OVERRIDE); none of them: A_WAIT.
+// The same decisions as nak_policy, without an action code that is built with selects and
+// decoded again with compares (tests/native_step compares the two for every h, a in 0..40).
+// The flags are conditions in scalar pairs: they cost no VALU.
+struct PolicyFlags {
+  bool adopt, relx, ovr;
+};
+template <int POL>
+__host__ __device__ inline CPR_AI PolicyFlags policy_flags(int32_t h, int32_t a) {
+  static_assert(POL >= P_HONEST && POL <= P_SM1, "built-in policies");
+  PolicyFlags f;
+  if constexpr (POL == P_HONEST) {
+    f.adopt = a < h;
+    f.ovr = a > h;
+    f.relx = f.ovr;
+  } else if constexpr (POL == P_SIMPLE) {
+    f.adopt = (h > 0) & (a < h);
+    f.ovr = (h > 0) & !(a < h);
+    f.relx = f.ovr;
+  } else if constexpr (POL == P_ES2014) {
+    // nak_policy's cases once a >= h: h <= 0 waits ((0, 1) and its last line); h > 0
+    // overrides at a - h == 1 (which covers (1, 2)) and matches otherwise ((1, 1) included);
+    // (2, 1) is a < h
+    f.adopt = a < h;
+    f.relx = !f.adopt & (h > 0);
+    f.ovr = f.relx & (a - h == 1);
+  } else {
+    const bool ma = (h == 1) & (a == 1);
+    const bool ov = (h == a - 1) & (h >= 1);
+    f.adopt = h > a;  // ma has h == a and ov has h < a: both exclude it, and each other
+    f.relx = ma | ov;
+    f.ovr = ov;
+  }
+  return f;
 }
 
 // ---- exact replay of one delivery window (used only when two deliveries tie in fp64)
@@ -516,10 +558,22 @@ __host__ __device__ inline CPR_AI uint64_t tie_table_d2(const NakParams& P, cons
   return on ? (1ull << (2 - miner)) : 0ull;  // bit j - 1, j = 3 - miner
 }
 
+// Packed tips, within one step (apply -> resolve -> activate; not part of pack()): the word
+// of the private-chain block apply's action releases up to, chain_ref(M, mf).w, and whether
+// the next activation delivers it to pub. Set by every apply_flags (and init); see there for
+// why resolve and activate may read them instead of forming the tip again. A base of the
+// packed lane alone: the lane over BRef tips keeps its size and layout (it lives in LDS and
+// in global memory in other kernels).
+struct StepTip {
+  uint32_t s_tip;
+  bool s_up;
+};
+struct NoStepTip {};
+
 // Tip: BRef, or PTip for the lanes of k_run_episodes_fused (d = 2, no block times, lazy
 // clock, ties by rule or deferred: what those kernels run and nothing else)
 template <class Tip>
-struct NakLaneT {
+struct NakLaneT : std::conditional<std::is_same<Tip, PTip>::value, StepTip, NoStepTip>::type {
   static constexpr bool PK = std::is_same<Tip, PTip>::value;
   using Mask = typename std::conditional<PK, uint32_t, uint64_t>::type;
   using Fork = typename std::conditional<PK, uint16_t, int32_t>::type;  // a fork height
@@ -595,6 +649,10 @@ struct NakLaneT {
     rlo = 1; rhi = 0; status = 0u; onA = 0ull; lca_da = 0;
     w_hasb = 0; w_bound = -__builtin_inf();
     qn = 0; rw = 0u; tinf = 0; esum = 0u;
+    if constexpr (PK) {
+      this->s_tip = 0u;
+      this->s_up = false;  // pend = -1: nothing to deliver at the first activation
+    }
   }
 
   // the same lane over BRef tips (a packed tip's k is not kept: 0)
@@ -770,8 +828,12 @@ struct NakLaneT {
     rhi = 0;
     // deliver the pending release to the attacker's public model (strict >)
     if constexpr (PK) {
-      const PTip r = chain_ref(M, pend);  // (its height is p0.h + pend where pend >= 0)
-      sel(pub, pend >= 0 && tip_h(r) > tip_h(pub), r);
+      // the tip and the test as apply_flags formed them (s_tip, s_up): since then resolve
+      // wrote neither p0 nor pub, and nothing else ran, so here chain_ref(M, pend) is that
+      // tip and tip_h(pub) the height it was compared with
+      CPR_HOST_ASSERT(this->s_up == (pend >= 0 && tip_h(chain_ref(M, pend)) > tip_h(pub)));
+      CPR_HOST_ASSERT(!this->s_up || this->s_tip == chain_ref(M, pend).w);
+      sel(pub, this->s_up, PTip{this->s_tip, (uint16_t)this->s_tip});
     } else {
       sel(pub, pend >= 0 && p0.h + pend > pub.h, chain_ref(M, pend));
     }
@@ -779,7 +841,11 @@ struct NakLaneT {
     {
       // the attacker's block joins the private chain (selects; only the time ring's stores
       // need the branch)
-      const bool deep = n + 1 >= M.cap;
+      // (packed tips with LaneMem::cap_test a compile-time false: the test and its selects
+      // fold away; the host build checks the launcher's premise)
+      const bool tested = !PK || M.cap_test;
+      CPR_HOST_ASSERT(tested || n + 1 < M.cap);
+      const bool deep = tested && n + 1 >= M.cap;
       const int32_t m = pick(deep, M.cap - 1, n + 1);
       if (M.times) {
         if (att) {
@@ -844,11 +910,19 @@ struct NakLaneT {
     else
       apply_refs(action);
   }
-  // packed tips: the same, with the forks' selects on Adopt and `fresh` merged into one on
-  // the combined condition (two selects and a min per fork instead of three)
+  // packed tips: the action code decoded, for callers that have one
   __host__ __device__ inline CPR_AI void apply_packed(int32_t action) {
-    const bool adopt = action == A_ADOPT;
-    const bool relx = action == A_MATCH || action == A_OVERRIDE;
+    apply_flags(action == A_ADOPT, action == A_MATCH || action == A_OVERRIDE,
+                action == A_OVERRIDE);
+  }
+  // packed tips: the same as apply_refs, with the forks' selects on Adopt and `fresh` merged
+  // into one on the combined condition (two selects and a min per fork instead of three).
+  // The action comes as the three tests apply makes of it (policy_flags gives them without
+  // an action code in between): Adopt; Match or Override; Override. relx excludes adopt,
+  // ovr implies relx
+  __host__ __device__ inline CPR_AI void apply_flags(bool adopt, bool relx, bool ovr) {
+    static_assert(PK, "packed tips only");
+    CPR_HOST_ASSERT(!(adopt && relx) && (!ovr || relx));
     const uint16_t hp = tip_h(pub);
     const bool fresh = (event & 2) != 0;
     const bool onch = pub.fork == hp;
@@ -857,13 +931,29 @@ struct NakLaneT {
     const bool af = adopt & fresh, an = adopt & !fresh;
     const uint16_t hpx = pick(onch, hp, (uint16_t)0xffffu);
     // pub.h - p0.h, signed, from the low halves
-    int32_t mf = (int32_t)(int16_t)(uint16_t)(pub.w - p0.w) + pick(action == A_OVERRIDE, 1, 0);
+    int32_t mf = (int32_t)(int16_t)(uint16_t)(pub.w - p0.w) + pick(ovr, 1, 0);
     mf = pick(mf < 0, 0, lo(mf, n));
     const bool newrel = relx & (mf > rel);
     rlo = pick(newrel, rel + 1, rlo);
     rhi = pick(newrel, mf, rhi);
     rel = pick(adopt, 0, pick(newrel, mf, rel));
     pend = pick(relx, mf, -1);
+    // The step's one released tip, chain block mf above p0 (0 <= mf <= n; chain_ref's
+    // word). Both later uses of a chain block in this step are this one:
+    //  * resolve selects chain_ref(M, rhi) into A only where `released` (rhi >= rlo). The
+    //    activation before this apply left rlo, rhi = 1, 0, and only the two picks above
+    //    write them since, so released holds exactly when newrel does, and then
+    //    rhi == mf == pend;
+    //  * the next activate delivers chain_ref(M, pend) to pub where pend >= 0 and it is
+    //    higher than pub. pend >= 0 exactly when relx (mf is clamped at 0).
+    // newrel implies relx, and relx excludes adopt, so in a step that uses the tip the
+    // picks below leave p0 as it is; resolve writes neither p0 nor pub (apply's write of
+    // pub.fork below leaves the height), and activate reads both before it writes pub. So
+    // p0 and tip_h(pub) read here are what resolve and activate would read.
+    CPR_HOST_ASSERT((p0.w & 0xffffu) + (uint32_t)mf <= 0xffffu &&
+                    (p0.w >> 16) + (uint32_t)mf <= 0xffffu);
+    this->s_tip = p0.w + (((uint32_t)mf << 16) | (uint32_t)mf);
+    this->s_up = relx & ((uint16_t)this->s_tip > hp);
     n_ba = pick(adopt, 0, n);
     n = pick(adopt, 0, n);
     b.fork = pick(af, tip_h(b), pick(an, lo16(b.fork, hpx), b.fork));
@@ -930,7 +1020,9 @@ struct NakLaneT {
     const bool released = rhi >= rlo && P.arrive;
     const uint32_t all = 3u;
     const bool dm = wminer != 0;
-    const uint16_t xh = (uint16_t)(tip_h(p0) + rhi);
+    // the released tip's height, tip_h(p0) + rhi where released (see the assertion below);
+    // elsewhere it is not used: newA and race hold only where released
+    const uint16_t xh = (uint16_t)this->s_tip;
     const uint16_t hs = (uint16_t)pick(onA != 0u, A.w, D.w);
     const uint16_t hb = tip_h(b);
     const uint16_t lca_new = pick(dm, b.fork, D.fork);
@@ -944,7 +1036,9 @@ struct NakLaneT {
     } else {
       status |= pick(race, (uint32_t)(ST_TIE | ST_TIE_UNRESOLVED), 0u);
     }
-    sel(A, newA, chain_ref(M, rhi));
+    // chain_ref(M, rhi) where released (newA implies it): the tip apply_flags formed
+    CPR_HOST_ASSERT(!(rhi >= rlo) || (rhi == pend && this->s_tip == chain_ref(M, rhi).w));
+    sel(A, newA, PTip{this->s_tip, (uint16_t)this->s_tip});
     lca_da = pick(newA, lca_new, lca_da);
     // dm ? (newA ? mask : 0) : (newA ? all : onA), with mask == all where the attacker mined
     onA = pick(newA, mask, pick(dm, 0u, onA));
